@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput bench of the MI355X tracking hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config c2|c5] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path -- ORB extraction, plane extraction,
 supposed planes from plane boundaries, the RGB-D Frame keypoint steps
@@ -20,8 +20,12 @@ the max time).
 Rank 0 prints ONE JSON line.  `value` = frames processed by all ranks / max
 over ranks of the timed region.  `roofline` is computed for the kernel with
 the largest share of the timed region, from HIP events recorded on its launch
-stream during the timed steps; `cpu_baseline` is the CPU oracle (one core) on
-a bounded sample of the same workload.
+stream during the timed steps.  A plain run sets up, warms up, times the K
+steps and prints the line.  --full adds the legs that take runs of their own:
+`cpu_baseline` (the CPU oracle, one core and all cores, on a bounded sample of
+the same workload), `open_loop_pose_agreement`, `closed_loop`,
+`single_sequence` and `ate` (tracked sequences against the CPU oracle).
+--dump-outputs DIR writes the last timed step's outputs as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -555,6 +559,57 @@ def ate_sequences(cfg, device, n_frames=300, n_seq=2):
         sp.close()
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(hp, res, out_dir):
+    """--dump-outputs: the arrays a caller of the timed step receives (HotPath.results() after the last timed
+    step; C3: also the LocalBundleAdjustment call's outputs), one DIR/<name>.npy each.  Record arrays are
+    written field by field (<name>.<field>.npy); float32 stays float32, everything else becomes float64 (exact
+    for the integer fields).  Per-keypoint arrays are zeroed past each frame's keypoint count (a caller reads
+    kp_counts[i] entries of frame i; the buffers are kp_cap long).  Where the set exceeds 64 MB (C5), the large
+    arrays are written as fixed samples: the elements at the sorted flat indices drawn by numpy's default_rng(0)."""
+    import numpy as np
+    arrays = {}
+
+    def add(name, a):
+        a = np.asarray(a)
+        if a.dtype.names:
+            for f in a.dtype.names:
+                add(f"{name}.{f}", a[f])
+            return
+        arrays[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+
+    live = np.arange(hp.kp_cap)[None, :] < np.asarray(res["kp_counts"]).reshape(-1, 1)  # (B, kp_cap)
+    for name, a in res.items():
+        a = np.asarray(a)
+        if a.shape[:2] == live.shape:
+            a = a.copy()
+            a[~live] = np.zeros((), a.dtype)
+        add(name, a)
+    if hp.n_lba:
+        # every in-flight slot optimises the same local maps: slot 0's keyframe poses, points, planes, outlier
+        # flags and result records (without the phase timers)
+        import spslam_lba
+        out = [t.cpu().numpy() for t in hp.lba_slots[0]["out"]]
+        for name, a in zip(("lba_keyframes", "lba_points", "lba_planes", "lba_point_outlier", "lba_plane_outlier"), out):
+            add(name, a)
+        rec = out[-1].view(spslam_lba.LBA_RESULT_DTYPE)
+        for f in ("iterations", "n_point_outliers", "n_plane_outliers", "status", "trials", "stopped"):
+            add(f"lba_result.{f}", rec[f])
+    out_dir = pathlib.Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    # smallest first, each array allowed an equal share of what is left: small arrays are written whole and only
+    # the large ones of a set above the limit are sampled
+    left = DUMP_LIMIT_BYTES - 4096 * len(arrays)  # (4 KiB: room for each .npy header)
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: (kv[1].nbytes, kv[0]))):
+        keep = left // (len(arrays) - i) // a.itemsize
+        if a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        left -= a.nbytes
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def _ensure_hw_queues(want=None):
     want = want or HW_QUEUES
     try:
@@ -582,6 +637,13 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="frames per step per GPU")
     ap.add_argument("--config", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--unique-frames", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the CPU baseline, the "
+                         "closed-loop line, the single-sequence line and the ATE check (each with its own option "
+                         "below); without it only the timed steps run and those legs are left out of the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (HotPath.results(), C3: the LocalBundleAdjustment "
+                         "results too) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=0,
                     help="timed one-core CPU baseline frames (default 300; 100 above 640x480)")
@@ -628,6 +690,9 @@ def main():
         print(json.dumps(single_sequence(pipeline.CONFIGS[args.config], 0, n_frames=args.single_sequence_frames,
                                          modes=(args.single_sequence_child == "pipelined",))))
         return
+    if not args.full:  # a plain run: the timed steps and their result line only
+        args.no_cpu_baseline = True
+        args.closed_loop_steps = args.single_sequence_frames = args.ate_frames = 0
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))  # one process per GPU (no launcher was used)
     rank = int(os.environ.get("RANK", "0"))
@@ -682,6 +747,8 @@ def main():
     elapsed = time.perf_counter() - t0
     times = {k: v for k, v in hp.kernel_times().items() if v[1] > 0}
     res = hp.results()
+    if args.dump_outputs:  # (rank r > 0 of a multi-GPU run: its own sequence, DIR/rank<r>)
+        dump_outputs(hp, res, args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"))
     ranks = per_rank(args.batch * args.steps, elapsed, dist, coll_dev)
     elapsed = max_over_ranks(elapsed, dist, coll_dev)
 
@@ -799,7 +866,7 @@ def main():
     cpu_poses = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"], cpu_poses = cpu_baseline(hp, timed=args.cpu_frames or (300 if hp.W * hp.H <= 640 * 480 else 100))
-    if rank == 0:
+    if rank == 0 and args.full:
         result["open_loop_pose_agreement"] = ate_report(hp, res, cpu_poses)
     hp.close()
     if rank == 0 and args.closed_loop_steps > 0:

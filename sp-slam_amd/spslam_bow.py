@@ -16,7 +16,9 @@ spslam_gpu.EXPORTED += ["spslam_bow_load_vocabulary", "spslam_bow_transform", "s
                         "spslam_search_by_bow", "spslam_search_by_bow_batch_device"]
 
 _P = ctypes.c_void_p
+# the in-repo vocabulary (tools/make_vocab.py): its text is stored as consecutive gzip parts
 VOCAB = pathlib.Path(__file__).resolve().parents[1] / "tests" / "golden" / "vocab_k6_l6.txt.gz"
+VOCAB_PARTS = [VOCAB.with_name(f"vocab_k6_l6.part{i}.txt.gz") for i in range(3)]
 
 
 class BowParams(ctypes.Structure):
@@ -31,6 +33,8 @@ class BowSide(ctypes.Structure):
 
 def read_vocabulary_text(path=VOCAB) -> bytes:
     path = pathlib.Path(path)
+    if path == VOCAB:
+        return b"".join(gzip.open(q, "rb").read() for q in VOCAB_PARTS)
     return gzip.open(path, "rb").read() if path.suffix == ".gz" else path.read_bytes()
 
 

@@ -1,5 +1,5 @@
 """Shared inputs of the bag-of-words tests: the in-repo DBoW2 vocabulary
-(tests/golden/vocab_k6_l6.txt.gz, trained by tools/make_vocab.py), ORB
+(tests/golden/vocab_k6_l6.part<i>.txt.gz, trained by tools/make_vocab.py), ORB
 features of synthetic frames (CPU oracle), and an independent pure-Python
 transcription of DBoW2's loadFromTextFile / transform and of
 ORBmatcher::SearchByBoW used to pin the C++ oracle."""
@@ -10,12 +10,12 @@ import pathlib
 import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-VOCAB = ROOT / "tests" / "golden" / "vocab_k6_l6.txt.gz"
+VOCAB_PARTS = [ROOT / "tests" / "golden" / f"vocab_k6_l6.part{i}.txt.gz" for i in range(3)]
 POP = np.array([bin(i).count("1") for i in range(256)], np.int32)
 
 
 def vocab_text():
-    return gzip.open(VOCAB, "rb").read()
+    return b"".join(gzip.open(p, "rb").read() for p in VOCAB_PARTS)
 
 
 def shape_vocab_text(k=10, L=6):

@@ -17,8 +17,8 @@ ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 @pytest.mark.parametrize("config", ["c2", "c4"])
 def test_two_ranks_on_one_gpu(config):
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--config", config, "--gpus", "2", "--rehearse-one-gpu", "--steps",
-           "3", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--ate-frames", "0", "--closed-loop-steps", "0"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--config", config, "--gpus", "2", "--rehearse-one-gpu", "--full",
+           "--steps", "3", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--ate-frames", "0", "--closed-loop-steps", "0"]
     if config != "c2":
         cmd += ["--single-sequence-frames", "0"]
     env = dict(os.environ, GPU_MAX_HW_QUEUES="8")

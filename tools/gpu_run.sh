@@ -6,7 +6,7 @@
 #   tests:F1,F2           pytest over the given test files only
 #   testsk:F1,F2:EXPR     pytest over the files with -k EXPR (_ for spaces); failing tests do not end the call
 #   smoke                 __graft_entry__.smoke()
-#   bench:CFG[:EXTRA]     python bench.py --config CFG --steps 20 --warmup 3 EXTRA (EXTRA: '_' for spaces)
+#   bench:CFG[:EXTRA]     python bench.py --config CFG --steps 20 --warmup 3 --full EXTRA (EXTRA: '_' for spaces)
 #   prof:CFG              rocprofv3 --kernel-trace --stats over a short bench of CFG (no CPU baseline / ATE)
 #   pmc:CFG               tools/pmc_round.sh CFG (HBM FETCH/WRITE passes, provenance = git HEAD)
 #   py:SCRIPT[:ARGS]      python SCRIPT ARGS (ARGS: '_' for spaces)
@@ -44,13 +44,13 @@ for step in "$@"; do
         bench)
             cfg=${arg%%:*}; extra=""
             [ "$cfg" != "$arg" ] && extra=$(echo "${arg#*:}" | tr '_' ' ')
-            timeout -k 10 600 python bench.py --config $cfg --steps 20 --warmup 3 $extra \
+            timeout -k 10 600 python bench.py --config $cfg --steps 20 --warmup 3 --full $extra \
                 > gpurun_out/${TAG}_bench_${cfg}.json 2> gpurun_out/${TAG}_bench_${cfg}.err \
                 || { tail -30 gpurun_out/${TAG}_bench_${cfg}.err; exit 1; }
             cut -c1-400 gpurun_out/${TAG}_bench_${cfg}.json ;;
         prof)
             timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_prof_${arg} -o run -- \
-                python3 bench.py --config $arg --steps 10 --warmup 2 --no-cpu-baseline --ate-frames 0 \
+                python3 bench.py --config $arg --steps 10 --warmup 2 --full --no-cpu-baseline --ate-frames 0 \
                 > gpurun_out/${TAG}_prof_${arg}.json 2> gpurun_out/${TAG}_prof_${arg}.err \
                 || { tail -30 gpurun_out/${TAG}_prof_${arg}.err; exit 1; } ;;
         pmc)

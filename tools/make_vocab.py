@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Train the in-repo DBoW2 vocabulary (tests/golden/vocab_k6_l6.txt.gz).
+"""Train the in-repo DBoW2 vocabulary (tests/golden/vocab_k6_l6.part{0,1,2}.txt.gz).
 
 The reference loads ORBvoc.txt (k = 10, L = 6, ~1M words) with
 TemplatedVocabulary::loadFromTextFile (src/System.cc:64), but that blob is not
@@ -25,7 +25,7 @@ frames from several scenes (sp-slam_amd/synth.py).  Deterministic (seeded).
 k = 6, L = 6 keeps the file small while Frame::ComputeBoW's levelsup = 4 still
 puts the FeatureVector at level 2, as with ORBvoc (36 nodes instead of 100).
 
-    python tools/make_vocab.py [--out tests/golden/vocab_k6_l6.txt.gz]
+    python tools/make_vocab.py [--out tests/golden/vocab_k6_l6.txt.gz]   (the stem of the part files)
 """
 from __future__ import annotations
 
@@ -166,8 +166,12 @@ def main():
         leaf = 0 if T.children[n] else 1
         lines.append(f"{T.parent[n]} {leaf} " + "".join(f"{int(b)} " for b in T.desc[n]) + f"{weight[n]:g}")
     text = "\n".join(lines) + "\n"
-    with gzip.open(args.out, "wt", compresslevel=9) as f:
-        f.write(text)
+    # written as three consecutive gzip parts (<out stem>.part<i>.txt.gz, each below 1 MiB), split at line ends
+    rows = text.splitlines(keepends=True)
+    per = -(-len(rows) // 3)
+    for i in range(3):
+        with gzip.open(args.out.replace(".txt.gz", f".part{i}.txt.gz"), "wt", compresslevel=9) as f:
+            f.write("".join(rows[i * per:(i + 1) * per]))
     depth_ok = all(T.children[c] for c in T.children[0])  # no leaf at level 1 (FeatureVector level 2 reached)
     print(f"{len(T.parent)} nodes, {len(leaves)} words, level-1 leaves: {not depth_ok}, {len(text) / 1e6:.1f} MB text "
           f"-> {args.out}", flush=True)
