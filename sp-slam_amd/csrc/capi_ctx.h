@@ -1,0 +1,282 @@
+// Private to the capi_*.cpp files: the context behind include/spslam_gpu.h, its device-buffer type, the error
+// helpers and the host-array staging of the drop-in entries.
+//
+// Nothing here falls back to a CPU path: if the HIP runtime or the gfx950 code object is unusable every entry
+// point returns SPSLAM_ERR_HIP.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "../../include/spslam_gpu.h"
+#include "orb_launch.h"
+#include "plane_launch.h"
+#include "pose_launch.h"
+#include "supposed_launch.h"
+#include "frame_launch.h"
+#include "lba_launch.h"
+#include "assoc_launch.h"
+#include "bow_launch.h"
+#include "match_launch.h"
+#include "track_launch.h"
+#include "grab_launch.h"
+
+using namespace spslam;
+
+// HIP-event timer per kernel kind; events recorded on the launch stream.
+struct EventTimer : KernelTimer {
+    struct Pair { int kind; hipEvent_t e0, e1; };
+    std::vector<Pair> pending;
+    std::vector<hipEvent_t> pool;
+    double total_ms[kNumKernelKinds] = {};
+    long long count[kNumKernelKinds] = {};
+    hipEvent_t cur[kNumKernelKinds] = {};
+    hipEvent_t get() {
+        if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
+        hipEvent_t e = nullptr;
+        (void)hipEventCreate(&e);
+        return e;
+    }
+    void begin(int kind, hipStream_t s) override { cur[kind] = get(); (void)hipEventRecord(cur[kind], s); }
+    void end(int kind, hipStream_t s) override {
+        hipEvent_t e1 = get();
+        (void)hipEventRecord(e1, s);
+        pending.push_back(Pair{kind, cur[kind], e1});
+    }
+    void collect() {
+        for (auto& p : pending) {
+            float ms = 0.f;
+            if (hipEventSynchronize(p.e1) == hipSuccess && hipEventElapsedTime(&ms, p.e0, p.e1) == hipSuccess) {
+                total_ms[p.kind] += ms;
+                count[p.kind] += 1;
+            }
+            pool.push_back(p.e0);
+            pool.push_back(p.e1);
+        }
+        pending.clear();
+    }
+    void reset() { collect(); for (int k = 0; k < kNumKernelKinds; k++) { total_ms[k] = 0; count[k] = 0; } }
+    ~EventTimer() override {
+        for (auto& p : pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
+        for (auto e : pool) (void)hipEventDestroy(e);
+    }
+};
+
+// Owning device buffer: pointer and capacity in bytes.  Reads as its T* wherever a pointer is expected.
+template <class T = uint8_t>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    operator T*() const { return p; }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // configure time: drop the old block whatever its size, then allocate exactly `bytes`
+    hipError_t alloc(size_t bytes) {
+        release();
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e == hipSuccess) cap = bytes; else p = nullptr;
+        return e;
+    }
+    // grow on demand: nothing when the capacity suffices, else wait for `s` (the work that may still read the
+    // old block) and reallocate
+    hipError_t reserve(size_t bytes, hipStream_t s) {
+        if (bytes <= cap) return hipSuccess;
+        const hipError_t e = hipStreamSynchronize(s);
+        return e != hipSuccess ? e : alloc(bytes);
+    }
+};
+
+// Streams, events and the host-mapped stop flag.  A base of the context so that they are destroyed after its
+// members: the device buffers are freed while the streams still exist.
+struct CtxStreams {
+    hipStream_t stream = nullptr;
+    hipStream_t orb_aux = nullptr;  // orb_launch's second stream (the small pyramid levels' chain)
+    hipEvent_t orb_fork = nullptr, orb_join = nullptr;
+    hipEvent_t lba_done = nullptr;    // recorded after each LBA launch: the next call's stream waits on it before it
+                                      //   rewrites the offsets, the ctl block or the scratch (one LBA call in flight
+                                      //   per context, whatever the streams)
+    int32_t* h_lba_stop = nullptr;    // host-mapped coherent pbStopFlag mirror of spslam_lba_optimize
+    int32_t* d_lba_stop = nullptr;    // its device alias (hipHostGetDevicePointer)
+    CtxStreams() = default;
+    CtxStreams(const CtxStreams&) = delete;
+    CtxStreams& operator=(const CtxStreams&) = delete;
+    ~CtxStreams() {
+        if (lba_done) (void)hipEventDestroy(lba_done);
+        if (h_lba_stop) (void)hipHostFree(h_lba_stop);
+        if (orb_fork) (void)hipEventDestroy(orb_fork);
+        if (orb_join) (void)hipEventDestroy(orb_join);
+        if (orb_aux) (void)hipStreamDestroy(orb_aux);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct spslam_ctx : CtxStreams {
+    int device = 0;
+    int num_cus = 256;  // compute units of the device (spslam_create)
+    spslam_orb_params p{};
+    std::string err;
+    // ORBextractor tables
+    std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
+    std::vector<int> nfeat;
+    int umax[16]{};
+    OrbGeom geom{};
+    long long pyr_frame_stride = 0, blur_frame_stride = 0;
+    int max_kp = 0;
+    // device buffers
+    DevBuf<> d_pyr, d_blur, d_score;
+    OrbBuffers b{};  // views of the six buffers below
+    DevBuf<uint32_t> d_cand, d_keys;
+    DevBuf<uint16_t> d_cand_cnt, d_keynode;
+    DevBuf<LevelKp> d_lvl_kp;
+    DevBuf<int> d_lvl_cnt;
+    DevBuf<> d_in;
+    DevBuf<spslam_keypoint> d_kps;
+    DevBuf<> d_desc;
+    DevBuf<int> d_cnt;
+    // last call (debug stage access)
+    const uint8_t* last_gray = nullptr;
+    size_t last_frame_stride = 0;
+    int last_stride = 0, last_frames = 0;
+    EventTimer* timer = nullptr;
+    // drop-in PoseOptimization staging
+    DevBuf<> d_pose_scratch;
+    // plane stage
+    bool planes_ready = false;
+    PlaneGeom pg{};
+    PlaneBuffers pb{};
+    float* plane_cloud[2] = {nullptr, nullptr};  // organized-cloud sets (spslam_planes_select_cloud_set)
+    int cloud_set = 0;
+    // the depth output whose cloud a fused grab wrote into each set (spslam_grab_fuse_cloud); null = none
+    struct CloudTag { const float* depth = nullptr; int n = 0; } cloud_tag[2];
+    bool grab_cloud = [] { const char* e = getenv("SPSLAM_GRAB_CLOUD"); return e && e[0] == '1'; }();
+    DevBuf<> d_plane_scratch;
+    DevBuf<float> d_depth_in;
+    DevBuf<spslam_plane> d_planes1;
+    DevBuf<int> d_plane_cnt1;
+    DevBuf<int32_t> d_inl1, d_con1;
+    int plane_last_frames = 0;
+    // supposed-plane stage (GeneratePlanesFromBoundries)
+    SuppParams sp{};
+    SuppBuffers sb{};
+    DevBuf<> d_supp_scratch;
+    DevBuf<spslam_supposed_plane> d_supp1;
+    DevBuf<int> d_supp_cnt1;
+    DevBuf<int32_t> d_line1;
+    DevBuf<float> d_patch1;
+    int supp_last_frames = 0;
+    // RGB-D frame stage (UndistortKeyPoints / ComputeStereoFromRGBD / AssignFeaturesToGrid)
+    bool frame_ready = false;
+    FrameGeom fg{};
+    DevBuf<> d_frame1;  // single-frame staging: kps, keys_un, depth, uR, grid_idx, grid_off, count
+    // LocalBundleAdjustment (all grown on demand)
+    DevBuf<> d_lba_scratch;
+    DevBuf<long long> d_lba_off;
+    int lba_stop_after = -1;          // spslam_lba_debug_stop_after
+    int lba_order = SPSLAM_LBA_G2O_ORDER;  // spslam_lba_set_order
+    int lba_team = 0;                 // spslam_lba_set_team (0: as many workgroups per problem as fill the chip)
+    DevBuf<int> d_lba_ctl;            // the g2o-order launch's tickets and team barrier counters
+    int pose_spin_cap = 0;            // spslam_debug_pose_spin_cap (0 = the kernel's default)
+    unsigned solve_fail_mask = 0;     // spslam_debug_force_solve_failures
+    DevBuf<> d_lba_stage;             // drop-in staging
+    DevBuf<int2> d_lba_work;          // (problem, first index) work tables + the active counter
+    // plane association: per (frame, frame plane, map plane) boundary distances
+    DevBuf<float> d_assoc_dist;
+    // projection matching: per (frame, last-frame point) windows + accepted-match lists
+    DevBuf<> d_match_scratch;
+    // bag of words: the vocabulary (one HBM blob), per-feature transform scratch, drop-in staging
+    DevBuf<> d_vocab;
+    VocabDev vocab{};
+    DevBuf<> d_bow_scratch;
+    DevBuf<> d_bow_stage;
+
+    // Call with the context's device current.  The last LBA launch may still read its buffers on a caller stream.
+    ~spslam_ctx() {
+        if (lba_done) (void)hipEventSynchronize(lba_done);
+        delete timer;
+    }
+};
+
+inline int fail(spslam_ctx* c, int code, const char* fmt, const char* what = "") {
+    if (c) {
+        char buf[512];
+        std::snprintf(buf, sizeof buf, fmt, what);
+        c->err = buf;
+    }
+    return code;
+}
+#define HIP_CHECK(ctx, expr)                                                                  \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess) return fail(ctx, SPSLAM_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); \
+    } while (0)
+
+// One slot of a drop-in entry's device block: `upload` bytes of the host array `src` go into `bytes` (>= upload)
+// bytes.  {src, n} uploads the whole slot; a bare size is an output-only slot.
+struct StageSlot {
+    const void* src;
+    size_t upload, bytes;
+    StageSlot(const void* s, size_t up, size_t b) : src(s), upload(up), bytes(b) {}
+    StageSlot(const void* s, size_t b) : StageSlot(s, b, b) {}
+    StageSlot(size_t b) : StageSlot(nullptr, 0, b) {}
+};
+
+// Slot offsets at 256-byte alignment; returns the block size.  No HIP call, so it can be checked on the CPU.
+inline size_t stage_layout(const StageSlot* slots, int n, size_t* off) {
+    size_t bytes = 0;
+    for (int i = 0; i < n; i++) { off[i] = bytes; bytes += (slots[i].bytes + 255) / 256 * 256; }
+    return bytes;
+}
+
+// The device block of a drop-in entry: laid out by stage_layout, uploaded on the context's stream.  The block is
+// either a stream-ordered temporary, returned on close() or when the Stage goes out of scope, or one of the
+// context's persistent buffers, which a need above its capacity grows to `grow` times that need.  open() and
+// close() return SPSLAM codes and leave the failing HIP call in the context's error string.
+struct Stage {
+    static constexpr int kMaxSlots = 18;
+    spslam_ctx* c;
+    uint8_t* q = nullptr;
+    bool temporary = false;
+    size_t off[kMaxSlots] = {};
+    explicit Stage(spslam_ctx* ctx) : c(ctx) {}
+    Stage(const Stage&) = delete;
+    Stage& operator=(const Stage&) = delete;
+    ~Stage() { if (temporary && q) (void)hipFreeAsync(q, c->stream); }
+    int open(std::initializer_list<StageSlot> slots, DevBuf<>* persistent = nullptr, size_t grow = 1) {
+        const int n = (int)slots.size();
+        if (n > kMaxSlots) return fail(c, SPSLAM_ERR_ARG, "too many staging slots%s", "");
+        const size_t bytes = stage_layout(slots.begin(), n, off);
+        if (!persistent) {
+            HIP_CHECK(c, hipMallocAsync((void**)&q, bytes, c->stream));
+            temporary = true;
+        } else {
+            if (bytes > persistent->cap) HIP_CHECK(c, persistent->reserve(bytes * grow, c->stream));
+            q = *persistent;
+        }
+        for (int i = 0; i < n; i++) {
+            const StageSlot& s = slots.begin()[i];
+            if (s.upload) HIP_CHECK(c, hipMemcpyAsync(q + off[i], s.src, s.upload, hipMemcpyHostToDevice, c->stream));
+        }
+        return SPSLAM_OK;
+    }
+    template <class T>
+    T* slot(int i) const { return (T*)(q + off[i]); }
+    int close() {
+        uint8_t* t = temporary ? q : nullptr;
+        q = nullptr;
+        if (t) HIP_CHECK(c, hipFreeAsync(t, c->stream));
+        return SPSLAM_OK;
+    }
+};

@@ -1,0 +1,467 @@
+// C ABI (include/spslam_gpu.h): projection and local-point search, the tracking graph, masked copies and bag of words.
+#include "capi_ctx.h"
+
+#include <cmath>
+#include <cstring>
+#include <sstream>
+
+namespace {
+
+// camera, image bounds, grid and level scales of the configured frame stage
+MatchGeom match_geom(const spslam_ctx* c) {
+    MatchGeom g{};
+    g.fx = c->fg.fx; g.fy = c->fg.fy; g.cx = c->fg.cx; g.cy = c->fg.cy; g.bf = c->fg.bf;
+    g.min_x = c->fg.min_x; g.max_x = c->fg.max_x; g.min_y = c->fg.min_y; g.max_y = c->fg.max_y;
+    g.ginv_x = c->fg.ginv_x; g.ginv_y = c->fg.ginv_y;
+    for (int l = 0; l < 8; l++) g.scale[l] = l < c->p.nlevels ? c->scale[l] : 0.f;
+    return g;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spslam_search_by_projection_batch_device(spslam_ctx* c, int n_frames, const spslam_proj_frame* d_frames,
+                                             const spslam_proj_point* d_points, int max_points,
+                                             const spslam_keypoint* d_keys_un, const uint8_t* d_desc,
+                                             const float* d_uright, const int32_t* d_grid_off,
+                                             const int32_t* d_grid_idx, const int* d_counts, int cap,
+                                             const spslam_match_params* params, int32_t* d_match, int* d_nmatches,
+                                             void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    if (n_frames < 1 || !d_frames || max_points < 0 || (max_points > 0 && !d_points) || !d_keys_un || !d_desc ||
+        !d_uright || !d_grid_off || !d_grid_idx || !d_counts || cap < 1 || cap > (1 << 20) || !params ||
+        !d_match || !d_nmatches)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_search_by_projection_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)hip_stream;  // NULL = the default stream (header)
+    const size_t n = (size_t)n_frames * std::max(max_points, 1);
+    const size_t need = n * sizeof(MatchWindow) + 256 + n * sizeof(int2);
+    HIP_CHECK(c, c->d_match_scratch.reserve(need, s));
+    auto* win = (MatchWindow*)c->d_match_scratch.p;
+    auto* pushes = (int2*)(c->d_match_scratch + ((n * sizeof(MatchWindow) + 255) & ~(size_t)255));
+    MatchCurrent cur{d_keys_un, d_desc, d_uright, d_grid_off, d_grid_idx, d_counts, cap};
+    HIP_CHECK(c, match_launch(n_frames, d_frames, d_points, max_points, cur, match_geom(c), *params, win, pushes,
+                              d_match, d_nmatches, s, c->timer));
+    return SPSLAM_OK;
+}
+
+int spslam_search_by_projection(spslam_ctx* c, const spslam_proj_frame* frame, const spslam_proj_point* points,
+                                const spslam_keypoint* keys_un, const uint8_t* desc, const float* uright, int n_kp,
+                                const int32_t* grid_off, const int32_t* grid_idx, const spslam_match_params* params,
+                                int32_t* match, int* nmatches) {
+    if (!c || !frame || !params || !grid_off || !nmatches || n_kp < 0 || frame->n_points < 0 ||
+        (frame->n_points && !points) || (n_kp && (!keys_un || !desc || !uright || !grid_idx || !match)))
+        return SPSLAM_ERR_ARG;
+    constexpr int kCells = SPSLAM_GRID_COLS * SPSLAM_GRID_ROWS;
+    if (grid_off[0] != 0 || grid_off[kCells] > n_kp)
+        return fail(c, SPSLAM_ERR_ARG, "grid CSR does not fit the keypoints%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    spslam_proj_frame F = *frame;
+    F.point_offset = 0;
+    const int np = F.n_points, cap = std::max(n_kp, 1);
+    const size_t K = (size_t)n_kp, C = (size_t)cap;
+    Stage st(c);
+    if (int rc = st.open({{&F, sizeof F},
+                           {points, np * sizeof(spslam_proj_point), std::max(np, 1) * sizeof(spslam_proj_point)},
+                           {keys_un, K * sizeof(spslam_keypoint), C * sizeof(spslam_keypoint)},
+                           {desc, K * 32, C * 32}, {uright, K * 4, C * 4},
+                           {grid_off, (kCells + 1) * 4}, {grid_idx, (size_t)grid_off[kCells] * 4, C * 4},
+                           {&n_kp, sizeof(int)}, C * 4, sizeof(int)}))
+        return rc;
+    int rc = spslam_search_by_projection_batch_device(
+        c, 1, st.slot<spslam_proj_frame>(0), st.slot<spslam_proj_point>(1), np, st.slot<spslam_keypoint>(2),
+        st.slot<uint8_t>(3), st.slot<float>(4), st.slot<int32_t>(5), st.slot<int32_t>(6), st.slot<int>(7), cap,
+        params, st.slot<int32_t>(8), st.slot<int>(9), c->stream);
+    if (rc) return rc;
+    if (n_kp) HIP_CHECK(c, hipMemcpyAsync(match, st.slot<int32_t>(8), K * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(nmatches, st.slot<int>(9), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+int spslam_search_local_points_batch_device(spslam_ctx* c, int n_frames, const spslam_local_frame* d_frames,
+                                            const spslam_local_point* d_points, int max_points,
+                                            const spslam_keypoint* d_keys_un, const uint8_t* d_desc,
+                                            const float* d_uright, const int32_t* d_grid_off,
+                                            const int32_t* d_grid_idx, const int* d_counts, int cap,
+                                            const uint8_t* d_taken, const spslam_local_params* params,
+                                            int32_t* d_match, int* d_nmatches, uint8_t* d_in_view,
+                                            const int32_t* d_seen, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    if (n_frames < 1 || !d_frames || max_points < 0 || (max_points > 0 && !d_points) || !d_keys_un || !d_desc ||
+        !d_uright || !d_grid_off || !d_grid_idx || !d_counts || cap < 1 || cap > (1 << 20) || !params ||
+        !d_match || !d_nmatches)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_search_local_points_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)hip_stream;  // NULL = the default stream (header)
+    const size_t need = (size_t)n_frames * std::max(max_points, 1) * sizeof(LocalWindow) + 256;
+    HIP_CHECK(c, c->d_match_scratch.reserve(need, s));
+    LocalConsts P{params->th, params->nn_ratio, params->view_cos_limit,
+                  std::log(c->p.scale_factor),  // Frame::mfLogScaleFactor = log(mfScaleFactor), float
+                  c->p.nlevels, d_seen};
+    MatchCurrent cur{d_keys_un, d_desc, d_uright, d_grid_off, d_grid_idx, d_counts, cap};
+    HIP_CHECK(c, local_match_launch(n_frames, d_frames, d_points, max_points, cur, match_geom(c), P, d_taken,
+                                    (LocalWindow*)c->d_match_scratch.p, d_match, d_nmatches, d_in_view, s, c->timer));
+    return SPSLAM_OK;
+}
+
+int spslam_search_local_points(spslam_ctx* c, const spslam_local_frame* frame, const spslam_local_point* points,
+                               const spslam_keypoint* keys_un, const uint8_t* desc, const float* uright, int n_kp,
+                               const int32_t* grid_off, const int32_t* grid_idx, const uint8_t* taken,
+                               const spslam_local_params* params, int32_t* match, int* nmatches, uint8_t* in_view) {
+    if (!c || !frame || !params || !grid_off || !nmatches || n_kp < 0 || frame->n_points < 0 ||
+        (frame->n_points && !points) || (n_kp && (!keys_un || !desc || !uright || !grid_idx || !match)))
+        return SPSLAM_ERR_ARG;
+    constexpr int kCells = SPSLAM_GRID_COLS * SPSLAM_GRID_ROWS;
+    if (grid_off[0] != 0 || grid_off[kCells] > n_kp)
+        return fail(c, SPSLAM_ERR_ARG, "grid CSR does not fit the keypoints%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    spslam_local_frame F = *frame;
+    F.point_offset = 0;
+    const int np = F.n_points, cap = std::max(n_kp, 1);
+    const size_t K = (size_t)n_kp, C = (size_t)cap;
+    Stage st(c);
+    if (int rc = st.open({{&F, sizeof F},
+                           {points, np * sizeof(spslam_local_point), std::max(np, 1) * sizeof(spslam_local_point)},
+                           {keys_un, K * sizeof(spslam_keypoint), C * sizeof(spslam_keypoint)},
+                           {desc, K * 32, C * 32}, {uright, K * 4, C * 4},
+                           {grid_off, (kCells + 1) * 4}, {grid_idx, (size_t)grid_off[kCells] * 4, C * 4},
+                           {&n_kp, sizeof(int)}, {taken, taken ? K : 0, C}, C * 4, sizeof(int),
+                           (size_t)std::max(np, 1)}))
+        return rc;
+    int rc = spslam_search_local_points_batch_device(
+        c, 1, st.slot<spslam_local_frame>(0), st.slot<spslam_local_point>(1), np, st.slot<spslam_keypoint>(2),
+        st.slot<uint8_t>(3), st.slot<float>(4), st.slot<int32_t>(5), st.slot<int32_t>(6), st.slot<int>(7), cap,
+        taken ? st.slot<uint8_t>(8) : nullptr, params, st.slot<int32_t>(9), st.slot<int>(10), st.slot<uint8_t>(11),
+        nullptr, c->stream);
+    if (rc) return rc;
+    if (n_kp) HIP_CHECK(c, hipMemcpyAsync(match, st.slot<int32_t>(9), K * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(nmatches, st.slot<int>(10), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (in_view && np) HIP_CHECK(c, hipMemcpyAsync(in_view, st.slot<uint8_t>(11), (size_t)np, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+int spslam_track_graph_batch_device(spslam_ctx* c, int n_frames, int stage, const spslam_track_batch* batch,
+                                    void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_frames < 1 || !batch || stage < SPSLAM_TRACK_MOTION_MODEL || stage > SPSLAM_TRACK_LAST_FRAME)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_track_graph_batch_device");
+    const spslam_track_batch& b = *batch;
+    const bool common = b.kp_counts && b.cap >= 1 && b.cap <= (1 << 20) && b.proj_frames && b.proj_match &&
+                        b.proj_points && b.edge_of_kp;
+    bool ok = common;
+    if (stage == SPSLAM_TRACK_MOTION_PRIOR) {
+        ok = b.proj_frames && b.velocity;
+    } else if (stage == SPSLAM_TRACK_LAST_FRAME) {
+        ok = common && b.keys_un && b.local_frames && b.local_points && b.local_match && b.results &&
+             b.point_outlier && b.point_outlier_local && b.next_frames && b.next_points && b.velocity;
+    } else if (stage == SPSLAM_TRACK_DISCARD) {
+        ok = ok && b.taken && b.local_frames && b.results && b.point_outlier;
+        if (b.next_match)  // the plane-outlier discard needs the first association and its edge flags
+            ok = ok && b.next_parallel && b.next_vertical && b.plane_outlier && b.assoc_match && b.assoc_parallel &&
+                 b.assoc_vertical && b.cap_a >= 0 && b.cap_b >= 0 && (b.cap_a == 0 || b.count_a) &&
+                 (b.cap_b == 0 || b.count_b);
+    } else {
+        ok = ok && b.keys_un && b.uright && b.problems && b.points && b.cap_a >= 0 && b.cap_b >= 0 &&
+             (b.cap_a == 0 || (b.planes_a && b.count_a && b.stride_a >= 16)) &&
+             (b.cap_b == 0 || (b.planes_b && b.count_b && b.stride_b >= 16)) &&
+             (b.cap_a + b.cap_b == 0 || (b.planes && b.map && b.assoc_match && b.assoc_parallel && b.assoc_vertical));
+        if (stage == SPSLAM_TRACK_LOCAL_MAP)
+            ok = ok && b.local_frames && b.local_points && b.local_match && b.results && b.point_outlier;
+    }
+    static const char* names[5] = {"MOTION_MODEL", "DISCARD", "LOCAL_MAP", "MOTION_PRIOR", "LAST_FRAME"};
+    if (!ok) return fail(c, SPSLAM_ERR_ARG, "missing buffer for stage %s of spslam_track_graph_batch_device",
+                         names[stage]);
+    HIP_CHECK(c, hipSetDevice(c->device));
+    TrackArgs a{};
+    a.b = b;
+    if (b.cap_b == 0) a.b.count_b = nullptr;
+    for (int l = 0; l < kMaxLevels; l++)
+        a.inv_sigma2[l] = c->inv_sigma2[std::min<int>(l, (int)c->inv_sigma2.size() - 1)];
+    HIP_CHECK(c, track_launch(n_frames, stage, a, (hipStream_t)hip_stream, c->timer));
+    return SPSLAM_OK;
+}
+
+int spslam_track_refkf_batch_device(spslam_ctx* c, int n_frames, int stage, const spslam_track_batch* mm,
+                                    const spslam_refkf_batch* rk, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_frames < 1 || !mm || !rk || (stage != SPSLAM_REFKF_PREPARE && stage != SPSLAM_REFKF_SELECT))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_track_refkf_batch_device");
+    const spslam_track_batch& b = *mm;
+    const spslam_refkf_batch& r = *rk;
+    bool ok = b.kp_counts && b.cap >= 1 && b.cap <= (1 << 20) && b.proj_frames && b.proj_points && b.proj_match &&
+              b.edge_of_kp && b.point_outlier && r.nmatches && r.fallback;
+    if (stage == SPSLAM_REFKF_PREPARE)
+        ok = ok && b.problems && b.planes && b.plane_outlier && r.refkf_counts;
+    else
+        ok = ok && r.bow_nmatches && r.bow_match && r.refkf_rows && r.refkf_index && r.rows_stride >= 1 &&
+             r.refkf_sets && r.assoc_frames && r.apply && r.refkf_match && r.refkf_frames && r.refkf_assoc &&
+             (!b.seen || b.local_frames);
+    if (!ok)
+        return fail(c, SPSLAM_ERR_ARG, "missing buffer for spslam_track_refkf_batch_device stage %s",
+                    stage == SPSLAM_REFKF_PREPARE ? "PREPARE" : "SELECT");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, refkf_launch(n_frames, stage, b, r, (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_track_refkf_vote_batch_device(spslam_ctx* c, int n_frames, const spslam_track_batch* mm,
+                                         const spslam_refkf_vote* vote, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_frames < 1 || !mm || !vote)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_track_refkf_vote_batch_device");
+    const spslam_track_batch& b = *mm;
+    const spslam_refkf_vote& v = *vote;
+    if (v.n_kf < 1 || v.n_kf > 1024 || v.ids_per_kf < 1 || v.new_kf >= v.n_kf)
+        return fail(c, SPSLAM_ERR_ARG, "spslam_track_refkf_vote_batch_device: n_kf outside 1 .. 1024, ids_per_kf < 1 "
+                    "or new_kf >= n_kf%s", "");
+    const bool ok = b.kp_counts && b.cap >= 1 && b.cap <= (1 << 20) && b.proj_frames && b.proj_points &&
+                    b.proj_match && b.edge_of_kp && b.point_outlier && v.kf_base && v.kf_sets && v.refkf_index &&
+                    v.refkf_sets;
+    if (!ok) return fail(c, SPSLAM_ERR_ARG, "missing buffer for spslam_track_refkf_vote_batch_device%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, refkf_vote_launch(n_frames, b, v, (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_masked_frame_copy_device(spslam_ctx* c, int n_frames, const uint8_t* flags, int n_regions,
+                                    const spslam_frame_region* regions, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_frames < 1 || !flags || n_regions < 0 || n_regions > kMaxFrameRegions || (n_regions && !regions))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_masked_frame_copy_device");
+    FrameRegions G{};
+    G.n = n_regions;
+    for (int k = 0; k < n_regions; k++) {
+        const spslam_frame_region& r = regions[k];
+        if (!r.dst || !r.src || r.frame_bytes < 0 || r.frame_bytes % 4 || r.dst_stride % 4 || r.src_stride % 4 ||
+            ((uintptr_t)r.dst | (uintptr_t)r.src) % 4 || r.frame_bytes > r.dst_stride || r.frame_bytes > r.src_stride)
+            return fail(c, SPSLAM_ERR_ARG, "bad region of %s", "spslam_masked_frame_copy_device");
+        G.r[k] = r;
+    }
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, masked_frame_copy_launch(n_frames, flags, G, (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+// ---------------------------------------------------------------- bag of words
+// TemplatedVocabulary::loadFromTextFile (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1424), host side,
+// then one HBM blob: descriptors, children CSR, weights, word ids.
+int spslam_bow_load_vocabulary(spslam_ctx* c, const char* text, size_t len, int* k_out, int* L_out, int* n_nodes_out,
+                               int* n_words_out) {
+    if (!c || (!text && len)) return SPSLAM_ERR_ARG;
+    std::istringstream f(std::string(text ? text : "", len));
+    std::string line;
+    std::getline(f, line);
+    std::stringstream ss;
+    ss << line;
+    int k = 0, L = 0, n1 = 0, n2 = 0;
+    ss >> k >> L >> n1 >> n2;
+    if (k < 0 || k > 20 || L < 1 || L > 10 || n1 < 0 || n1 > 5 || n2 < 0 || n2 > 3)
+        return fail(c, SPSLAM_ERR_ARG, "vocabulary header is not DBoW2 text%s", "");
+    std::vector<int> parent(1, 0);
+    std::vector<std::vector<int>> children(1);
+    std::vector<uint8_t> desc(32, 0);
+    std::vector<double> weight(1, 0.0);
+    std::vector<uint32_t> word(1, 0);
+    uint32_t n_words = 0;
+    while (!f.eof()) {  // the reference's loop: an empty last line still makes a node
+        std::string sn;
+        std::getline(f, sn);
+        std::stringstream sl;
+        sl << sn;
+        const int nid = (int)parent.size();
+        int pid = 0, leaf = 0;
+        sl >> pid;
+        if (pid < 0 || pid >= nid) return fail(c, SPSLAM_ERR_ARG, "vocabulary node with a bad parent%s", "");
+        sl >> leaf;
+        std::stringstream sd;
+        for (int i = 0; i < 32; i++) {
+            std::string e;
+            sl >> e;
+            sd << e << " ";
+        }
+        uint8_t d[32] = {0};  // FORB::fromString leaves unparsed bytes unset (uninitialised there, zero here)
+        for (int i = 0; i < 32; i++) {
+            int v;
+            sd >> v;
+            if (!sd.fail()) d[i] = (uint8_t)v;
+        }
+        double w = 0.0;
+        sl >> w;
+        parent.push_back(pid);
+        children.emplace_back();
+        children[pid].push_back(nid);
+        desc.insert(desc.end(), d, d + 32);
+        weight.push_back(w);
+        word.push_back(leaf > 0 ? n_words++ : 0u);
+    }
+    const int n = (int)parent.size();
+    std::vector<int> cbeg(n), ccnt(n), cids;
+    cids.reserve(n);
+    for (int i = 0; i < n; i++) {
+        cbeg[i] = (int)cids.size();
+        ccnt[i] = (int)children[i].size();
+        cids.insert(cids.end(), children[i].begin(), children[i].end());
+    }
+    if (cids.empty()) cids.push_back(0);
+    const size_t sz[] = {(size_t)n * 32, (size_t)n * 4, (size_t)n * 4, cids.size() * 4, (size_t)n * 8, (size_t)n * 4};
+    size_t off[6], bytes = 0;
+    for (int i = 0; i < 6; i++) { off[i] = bytes; bytes += (sz[i] + 255) / 256 * 256; }
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    c->vocab = VocabDev{};
+    HIP_CHECK(c, c->d_vocab.alloc(bytes));
+    const void* src[] = {desc.data(), cbeg.data(), ccnt.data(), cids.data(), weight.data(), word.data()};
+    for (int i = 0; i < 6; i++) HIP_CHECK(c, hipMemcpy(c->d_vocab + off[i], src[i], sz[i], hipMemcpyHostToDevice));
+    VocabDev& V = c->vocab;
+    V.n_nodes = n; V.k = k; V.L = L; V.scoring = n1; V.weighting = n2;
+    V.desc = (const uint4*)(c->d_vocab + off[0]);
+    V.child_begin = (const int*)(c->d_vocab + off[1]);
+    V.child_count = (const int*)(c->d_vocab + off[2]);
+    V.child_ids = (const int*)(c->d_vocab + off[3]);
+    V.weight = (const double*)(c->d_vocab + off[4]);
+    V.word_id = (const uint32_t*)(c->d_vocab + off[5]);
+    if (k_out) *k_out = k;
+    if (L_out) *L_out = L;
+    if (n_nodes_out) *n_nodes_out = n;
+    if (n_words_out) *n_words_out = (int)n_words;
+    return SPSLAM_OK;
+}
+
+int spslam_bow_transform_batch_device(spslam_ctx* c, int n_frames, const uint8_t* d_desc, const int* d_counts,
+                                      int cap, int levelsup, uint32_t* d_bow_words, double* d_bow_values,
+                                      int* d_n_bow, uint32_t* d_fv_nodes, int32_t* d_fv_start,
+                                      int32_t* d_fv_features, int* d_n_fv, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!c->d_vocab) return fail(c, SPSLAM_ERR_NOT_READY, "no vocabulary loaded (spslam_bow_load_vocabulary)%s", "");
+    if (n_frames < 1 || !d_desc || !d_counts || cap < 1 || cap > 8192 || !d_bow_words || !d_bow_values || !d_n_bow ||
+        !d_fv_nodes || !d_fv_start || !d_fv_features || !d_n_fv)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_bow_transform_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (c->vocab.n_nodes < 2) {  // empty vocabulary: transform clears both vectors
+        HIP_CHECK(c, hipMemsetAsync(d_n_bow, 0, (size_t)n_frames * sizeof(int), s));
+        HIP_CHECK(c, hipMemsetAsync(d_n_fv, 0, (size_t)n_frames * sizeof(int), s));
+        return SPSLAM_OK;
+    }
+    const size_t n = (size_t)n_frames * cap;
+    const size_t need = n * 16 + 512;
+    HIP_CHECK(c, c->d_bow_scratch.reserve(need, s));
+    auto* s_weight = (double*)c->d_bow_scratch.p;
+    auto* s_word = (uint32_t*)(c->d_bow_scratch + ((n * 8 + 255) & ~(size_t)255));
+    auto* s_node = s_word + ((n + 63) & ~(size_t)63);
+    BowOut out{d_bow_words, d_bow_values, d_n_bow, d_fv_nodes, d_fv_start, d_fv_features, d_n_fv};
+    HIP_CHECK(c, bow_transform_launch(c->vocab, n_frames, d_desc, d_counts, cap, levelsup, s_word, s_weight, s_node,
+                                      out, s, c->timer));
+    return SPSLAM_OK;
+}
+
+int spslam_bow_transform(spslam_ctx* c, const uint8_t* desc, int n, int levelsup, uint32_t* bow_words,
+                         double* bow_values, int* n_bow, uint32_t* fv_nodes, int32_t* fv_start,
+                         int32_t* fv_features, int* n_fv) {
+    if (!c || n < 0 || (n && !desc) || !n_bow || !n_fv || n > 8192 || !fv_start ||
+        (n && (!bow_words || !bow_values || !fv_nodes || !fv_features)))
+        return SPSLAM_ERR_ARG;
+    if (!c->d_vocab) return fail(c, SPSLAM_ERR_NOT_READY, "no vocabulary loaded (spslam_bow_load_vocabulary)%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const int cap = std::max(n, 1);
+    const size_t C = (size_t)cap;
+    Stage st(c);
+    if (int rc = st.open({{desc, (size_t)n * 32, C * 32}, {&n, 4}, C * 4, C * 8, 4, C * 4, (C + 1) * 4, C * 4, 4},
+                         &c->d_bow_stage))
+        return rc;
+    int rc = spslam_bow_transform_batch_device(c, 1, st.slot<uint8_t>(0), st.slot<int>(1), cap, levelsup,
+                                               st.slot<uint32_t>(2), st.slot<double>(3), st.slot<int>(4),
+                                               st.slot<uint32_t>(5), st.slot<int32_t>(6), st.slot<int32_t>(7),
+                                               st.slot<int>(8), c->stream);
+    if (rc) return rc;
+    HIP_CHECK(c, hipMemcpyAsync(n_bow, st.slot<int>(4), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(n_fv, st.slot<int>(8), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    if (*n_bow) {
+        HIP_CHECK(c, hipMemcpy(bow_words, st.slot<void>(2), (size_t)*n_bow * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(c, hipMemcpy(bow_values, st.slot<void>(3), (size_t)*n_bow * 8, hipMemcpyDeviceToHost));
+    }
+    if (*n_fv) {
+        HIP_CHECK(c, hipMemcpy(fv_nodes, st.slot<void>(5), (size_t)*n_fv * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(c, hipMemcpy(fv_start, st.slot<void>(6), (size_t)(*n_fv + 1) * 4, hipMemcpyDeviceToHost));
+        int m = 0;
+        std::memcpy(&m, fv_start + *n_fv, 4);
+        if (m) HIP_CHECK(c, hipMemcpy(fv_features, st.slot<void>(7), (size_t)m * 4, hipMemcpyDeviceToHost));
+    } else {
+        fv_start[0] = 0;
+    }
+    return SPSLAM_OK;
+}
+
+int spslam_search_by_bow_batch_device(spslam_ctx* c, int n_pairs, const int32_t* d_pairs,
+                                      const spslam_bow_side* kf, const spslam_bow_side* fr,
+                                      const spslam_bow_params* params, int32_t* d_match, int* d_nmatches,
+                                      void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    auto side_ok = [](const spslam_bow_side* b, bool keyframe) {
+        return b && b->desc && b->keys && b->counts && b->fv_nodes && b->fv_start && b->fv_features && b->n_fv &&
+               b->cap >= 1 && b->cap <= 8192 && (!keyframe || b->has_point);
+    };
+    if (n_pairs < 1 || !d_pairs || !side_ok(kf, true) || !side_ok(fr, false) || !params || !d_match || !d_nmatches)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_search_by_bow_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    BowSide K{kf->desc, kf->keys, kf->has_point, kf->counts, kf->fv_nodes, kf->fv_start, kf->fv_features, kf->n_fv,
+              kf->cap};
+    BowSide F{fr->desc, fr->keys, nullptr, fr->counts, fr->fv_nodes, fr->fv_start, fr->fv_features, fr->n_fv, fr->cap};
+    HIP_CHECK(c, bow_search_launch(n_pairs, (const int2*)d_pairs, K, F, params->nn_ratio, params->check_orientation,
+                                   d_match, d_nmatches, (hipStream_t)hip_stream, c->timer));
+    return SPSLAM_OK;
+}
+
+int spslam_search_by_bow(spslam_ctx* c, const uint8_t* kf_desc, const spslam_keypoint* kf_keys,
+                         const uint8_t* kf_has_point, int kf_n, const uint32_t* kf_fv_nodes,
+                         const int32_t* kf_fv_start, const int32_t* kf_fv_features, int kf_n_fv,
+                         const uint8_t* f_desc, const spslam_keypoint* f_keys, int f_n, const uint32_t* f_fv_nodes,
+                         const int32_t* f_fv_start, const int32_t* f_fv_features, int f_n_fv,
+                         const spslam_bow_params* params, int32_t* match, int* nmatches) {
+    if (!c || !params || !nmatches || kf_n < 0 || f_n < 0 || kf_n > 8192 || f_n > 8192 || kf_n_fv < 0 ||
+        f_n_fv < 0 || kf_n_fv > std::max(kf_n, 1) || f_n_fv > std::max(f_n, 1) || !kf_fv_start || !f_fv_start ||
+        (kf_n && (!kf_desc || !kf_keys || !kf_has_point)) || (f_n && (!f_desc || !f_keys || !match)) ||
+        (kf_n_fv && (!kf_fv_nodes || !kf_fv_features)) || (f_n_fv && (!f_fv_nodes || !f_fv_features)))
+        return SPSLAM_ERR_ARG;
+    const int kc = std::max(kf_n, 1), fc = std::max(f_n, 1);
+    const int km = kf_fv_start[kf_n_fv], fm = f_fv_start[f_n_fv];
+    if (km < 0 || km > kf_n || fm < 0 || fm > f_n)
+        return fail(c, SPSLAM_ERR_ARG, "FeatureVector does not fit the features%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    // keyframe slot 0 and frame slot 0 of a one-pair batch
+    const size_t kn = (size_t)kf_n, fn = (size_t)f_n, KC = (size_t)kc, FC = (size_t)fc;
+    const int32_t pair[2] = {0, 0};
+    Stage st(c);
+    constexpr size_t kKp = sizeof(spslam_keypoint);
+    if (int rc = st.open({{kf_desc, kn * 32, KC * 32}, {kf_keys, kn * kKp, KC * kKp}, {kf_has_point, kn, KC},
+                           {&kf_n, 4}, {kf_fv_nodes, (size_t)kf_n_fv * 4, KC * 4},
+                           {kf_fv_start, (size_t)(kf_n_fv + 1) * 4, (KC + 1) * 4},
+                           {kf_fv_features, (size_t)km * 4, KC * 4}, {&kf_n_fv, 4},
+                           {f_desc, fn * 32, FC * 32}, {f_keys, fn * kKp, FC * kKp}, {&f_n, 4},
+                           {f_fv_nodes, (size_t)f_n_fv * 4, FC * 4},
+                           {f_fv_start, (size_t)(f_n_fv + 1) * 4, (FC + 1) * 4},
+                           {f_fv_features, (size_t)fm * 4, FC * 4}, {&f_n_fv, 4}, {pair, 8}, FC * 4, 4},
+                         &c->d_bow_stage))
+        return rc;
+    spslam_bow_side K{st.slot<uint8_t>(0), st.slot<spslam_keypoint>(1), st.slot<uint8_t>(2), st.slot<int>(3),
+                      st.slot<uint32_t>(4), st.slot<int32_t>(5), st.slot<int32_t>(6), st.slot<int>(7), kc, 0};
+    spslam_bow_side F{st.slot<uint8_t>(8), st.slot<spslam_keypoint>(9), nullptr, st.slot<int>(10),
+                      st.slot<uint32_t>(11), st.slot<int32_t>(12), st.slot<int32_t>(13), st.slot<int>(14), fc, 0};
+    int rc = spslam_search_by_bow_batch_device(c, 1, st.slot<int32_t>(15), &K, &F, params, st.slot<int32_t>(16),
+                                               st.slot<int>(17), c->stream);
+    if (rc) return rc;
+    if (f_n) HIP_CHECK(c, hipMemcpyAsync(match, st.slot<int32_t>(16), fn * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(nmatches, st.slot<int>(17), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+}  // extern "C"
