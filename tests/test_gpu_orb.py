@@ -8,6 +8,8 @@ Reference: src/ORBextractor.cc (stage line numbers in the test names' docstrings
 import numpy as np
 import pytest
 
+from orb_common import assert_kps_equal as _assert_kps_equal, assert_stages_equal
+
 pytestmark = pytest.mark.gpu
 
 
@@ -25,13 +27,6 @@ def oracle():
     return oracle_ctypes.OrbOracle()
 
 
-def _assert_kps_equal(a, b, what):
-    assert len(a) == len(b), f"{what}: count {len(a)} vs {len(b)}"
-    for f in ("x", "y", "size", "angle", "response", "octave", "class_id"):
-        bad = np.nonzero(a[f] != b[f])[0]
-        assert bad.size == 0, f"{what}: field {f} differs at {bad[:10]} ({a[f][bad[:3]]} vs {b[f][bad[:3]]})"
-
-
 def test_tables_match_oracle(gpu, oracle):
     """ORBextractor ctor tables, src/ORBextractor.cc:415-446."""
     t = gpu.tables()
@@ -47,17 +42,7 @@ def test_stages_bit_exact(gpu, oracle, synth_frames, fi):
     g = synth_frames[fi][0]
     gpu(g)
     oracle.pyramid(g)
-    for level in range(8):
-        assert np.array_equal(gpu.debug_stage(0, level, 0), oracle.level_image(level)), f"pyramid L{level}"
-        assert np.array_equal(gpu.debug_stage(0, level, 1), oracle.level_blurred(level)), f"blur L{level}"
-        cg, co = gpu.debug_stage(0, level, 2), oracle.level_candidates(level)
-        assert len(cg) == len(co), f"candidates L{level}: {len(cg)} vs {len(co)}"
-        for f in ("x", "y", "response"):
-            assert np.array_equal(cg[f], co[f]), f"candidates L{level} field {f}"
-        kg, ko = gpu.debug_stage(0, level, 3), oracle.level_keypoints(level)
-        assert len(kg) == len(ko), f"octree L{level}: {len(kg)} vs {len(ko)}"
-        for f in ("x", "y", "response", "octave", "size"):
-            assert np.array_equal(kg[f], ko[f]), f"octree L{level} field {f}"
+    assert_stages_equal(gpu, oracle, 8)
 
 
 @pytest.mark.parametrize("fi", [0, 1, 2, 3])
