@@ -971,6 +971,100 @@ typedef struct spslam_refkf_vote {
 
 int spslam_track_refkf_vote_batch_device(spslam_ctx* ctx, int n_frames, const spslam_track_batch* mm,
                                          const spslam_refkf_vote* vote, void* hip_stream);
+/* Deviation of spslam_refkf_vote: the reference credits every keyframe in pMP->GetObservations() (:1474-1476);
+ * this vote credits only the keyframe that created the point.  The two agree while each point has one observer,
+ * which stops holding once LocalMapping adds observations.  spslam_track_update_local_map_batch_device below
+ * votes over the observer lists. */
+
+/* Tracking::UpdateLocalMap (src/Tracking.cc:1427-1571): UpdateLocalKeyFrames (:1463-1571) then UpdateLocalPoints
+ * (:1437-1460), per frame, batched, on a device-resident map that the host maintains.  One workgroup per frame.
+ *   Votes (:1466-1483): every current-frame keypoint with a map point that is not bad adds one vote to every
+ *     keyframe of that point's observer list.
+ *   K1 (:1485-1510): no keyframe with a vote -> return before clear(): local_kfs / n_local_kfs keep what they
+ *     held (they are IN / OUT per frame slot) and kf_max = -1.  Otherwise the list is cleared and the voted
+ *     keyframes that are not bad are appended in ascending keyframe index; kf_max = the first strict maximum
+ *     among them (-1 when all voters are bad: the list is then empty).
+ *   Neighbours (:1513-1564): for each of the first K1 entries, in order: stop when the list holds > 80 (checked
+ *     before each entry); append the first of the entry's <= 10 best covisible keyframes
+ *     (GetBestCovisibilityKeyFrames(10), KeyFrame.cc:179) that is not bad and not yet in the list; append the first
+ *     child that is not bad and not in the list; if the parent exists and is not in the list append it (no bad
+ *     check, as the reference) and end the whole loop (the break at :1560 leaves the outer for).
+ *   Local points (:1437-1460): the local keyframes' GetMapPointMatches() concatenated in list order then keypoint
+ *     order, empty slots and bad points dropped, the first occurrence of each point kept.
+ * Every index in the tables is local to the frame's sequence: keyframe k of frame f is entry kf_base[f] + k of the
+ * keyframe tables, point row r is entry row_base[f] + r of the point tables, so many sequences share one call.
+ * Entries outside [0, n_kf) / [0, scratch_stride) are ignored.
+ * Deviations from the reference:
+ *   - keyframes and children are walked in ascending index where the reference has pointer order
+ *     (std::map<KeyFrame*>, std::set<KeyFrame*>), as everywhere at this ABI;
+ *   - the neighbour pass iterates the first K1 entries by index.  The reference iterates the vector it appends
+ *     to after reserve(3 * K1); K1 + 2 (K1 - 1) + 3 appends can reallocate under the iterator, which is
+ *     undefined.  This is the defined reading;
+ *   - mCurrentFrame.mvpMapPoints[i] = NULL for a bad point (:1480) is left to the caller: the bad point only
+ *     casts no vote;
+ *   - mnTrackReferenceForFrame stamps are not written anywhere: membership lives in the workgroup's LDS and
+ *     in `scratch`. */
+typedef struct spslam_local_map {
+    /* the frames' own map points: either frame_rows, or (frame_rows == NULL) the mm batch, read as
+     * spslam_track_refkf_vote_batch_device reads it: for every keypoint i with an edge that is not an outlier,
+     * id = proj_points[point_offset + proj_match[i]].id, row = id_to_row ? id_to_row[id_base[f] + id] : id */
+    const int32_t* frame_rows;    /* f * cap + i: the keypoint's point row, -1 = none (may be NULL) */
+    const int* kp_counts;         /* with frame_rows: keypoints per frame */
+    const int32_t* id_to_row;     /* mm path: map point id -> row, -1 = none (may be NULL) */
+    const int32_t* id_base;       /* mm path, per frame: its sequence's first entry of id_to_row (NULL = 0) */
+    const int32_t* kf_base;       /* per frame: its sequence's keyframe 0 in the keyframe tables */
+    const int32_t* row_base;      /* per frame: its sequence's row 0 in the point tables */
+    int32_t cap;                  /* with frame_rows: keypoint slots per frame */
+    int32_t n_kf;                 /* keyframes per sequence, 1 .. 1024 */
+    /* per point row */
+    const int32_t* obs_off;       /* CSR (rows + 1): the row's observers in obs_kf */
+    const int32_t* obs_kf;        /* observer keyframes, ascending (MapPoint::GetObservations) */
+    const uint8_t* point_bad;     /* MapPoint::isBad (may be NULL: none) */
+    const spslam_local_point* points;  /* the records (required with out->records) */
+    /* per keyframe */
+    const uint8_t* kf_bad;        /* KeyFrame::isBad (may be NULL: none) */
+    const int32_t* covis;         /* 10 per keyframe: GetBestCovisibilityKeyFrames(10), best first, -1 padded */
+    const int32_t* child_off;     /* CSR (keyframes + 1) */
+    const int32_t* child;         /* GetChilds, ascending */
+    const int32_t* parent;        /* GetParent, -1 = none */
+    const int32_t* match_off;     /* CSR (keyframes + 1) */
+    const int32_t* match_row;     /* GetMapPointMatches in keypoint order: the point's row or -1 */
+} spslam_local_map;
+
+typedef struct spslam_local_map_out {
+    const int8_t* state;          /* per frame: 2 = LOST (spslam_refkf_batch.state): the frame is skipped entirely,
+                                     nothing of it is written (:406-409); may be NULL */
+    int32_t* local_kfs;           /* IN / OUT, f * kf_cap: mvpLocalKeyFrames */
+    int32_t* n_local_kfs;         /* IN / OUT per frame */
+    int32_t* kf_max;              /* out per frame: pKFmax, -1 = none */
+    int32_t* local_rows;          /* out, f * capacity: mvpLocalMapPoints as point rows */
+    int32_t* n_local;             /* out per frame */
+    int32_t* status;              /* out per frame: 0 ok, 1 = the point list exceeded capacity (its first capacity
+                                     entries are written, n_local = capacity) */
+    int32_t* scratch;             /* f * scratch_stride: the de-duplication's first position per row.  Its contents
+                                     on entry do not matter and need no memset between calls */
+    int32_t kf_cap;               /* >= n_kf */
+    int32_t capacity;             /* >= 0 */
+    int32_t scratch_stride;       /* > every row of a sequence */
+    int32_t pad;
+    spslam_local_point* records;  /* out (may be NULL), f * capacity: points[row_base[f] + local_rows[..]] in order */
+    spslam_local_frame* local_frames;  /* with records: point_offset = f * capacity and n_points = n_local are
+                                     written, Tcw / seen_offset / stamp are left as they are, so that
+                                     spslam_search_local_points_batch_device runs on the output directly */
+} spslam_local_map_out;
+
+/* mm may be NULL when map->frame_rows is given. */
+int spslam_track_update_local_map_batch_device(spslam_ctx* ctx, int n_frames, const spslam_track_batch* mm,
+                                               const spslam_local_map* map, const spslam_local_map_out* out,
+                                               void* hip_stream);
+
+/* Drop-in for one frame on host arrays: the same two structs holding host pointers.  map: frame_rows (n_kp
+ * entries) is required; kp_counts, id_to_row, id_base, kf_base, row_base and cap are ignored (one sequence at base
+ * 0); the tables hold n_rows point rows and map->n_kf keyframes.  out: state, scratch, scratch_stride and kf_cap
+ * are ignored (local_kfs holds n_kf entries, IN / OUT as above); local_frames, when given with records, is one
+ * frame whose point_offset becomes 0. */
+int spslam_track_update_local_map(spslam_ctx* ctx, const spslam_local_map* map, int n_rows, int n_kp,
+                                  const spslam_local_map_out* out);
 
 /* dst[f] = src[f] for every frame f with flags[f] != 0, region by region: frame f's bytes at dst + f * dst_stride
  * and src + f * src_stride (sizes and strides multiples of 4; at most 32 regions per call). */

@@ -230,6 +230,127 @@ int spslam_track_refkf_vote_batch_device(spslam_ctx* c, int n_frames, const spsl
     return SPSLAM_OK;
 }
 
+int spslam_track_update_local_map_batch_device(spslam_ctx* c, int n_frames, const spslam_track_batch* mm,
+                                               const spslam_local_map* map, const spslam_local_map_out* out,
+                                               void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_frames < 1 || !map || !out)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_track_update_local_map_batch_device");
+    const spslam_local_map& m = *map;
+    const spslam_local_map_out& o = *out;
+    if (m.n_kf < 1 || m.n_kf > 1024)
+        return fail(c, SPSLAM_ERR_ARG, "spslam_track_update_local_map_batch_device: n_kf outside 1 .. 1024%s", "");
+    if (o.capacity < 0 || o.kf_cap < 0 || o.scratch_stride < 0 || o.kf_cap < m.n_kf)
+        return fail(c, SPSLAM_ERR_ARG, "spslam_track_update_local_map_batch_device: negative capacity, kf_cap or "
+                    "scratch_stride, or kf_cap < n_kf%s", "");
+    bool ok = m.kf_base && m.row_base && m.obs_off && m.obs_kf && m.covis && m.child_off && m.child && m.parent &&
+              m.match_off && m.match_row && o.local_kfs && o.n_local_kfs && o.kf_max && o.local_rows && o.n_local &&
+              o.status && o.scratch && (!o.records || m.points);
+    if (m.frame_rows)
+        ok = ok && m.kp_counts && m.cap >= 1 && m.cap <= (1 << 20);
+    else
+        ok = ok && mm && mm->kp_counts && mm->cap >= 1 && mm->cap <= (1 << 20) && mm->proj_frames &&
+             mm->proj_points && mm->proj_match && mm->edge_of_kp && mm->point_outlier;
+    if (!ok) return fail(c, SPSLAM_ERR_ARG, "missing buffer for spslam_track_update_local_map_batch_device%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, update_local_map_launch(n_frames, m.frame_rows ? nullptr : mm, m, o, (hipStream_t)hip_stream,
+                                         c->timer));
+    return SPSLAM_OK;
+}
+
+int spslam_track_update_local_map(spslam_ctx* c, const spslam_local_map* map, int n_rows, int n_kp,
+                                  const spslam_local_map_out* out) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!map || !out || n_rows < 0 || n_kp < 0)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_track_update_local_map");
+    const spslam_local_map& m = *map;
+    const spslam_local_map_out& o = *out;
+    if (m.n_kf < 1 || m.n_kf > 1024)
+        return fail(c, SPSLAM_ERR_ARG, "spslam_track_update_local_map: n_kf outside 1 .. 1024%s", "");
+    if (o.capacity < 0) return fail(c, SPSLAM_ERR_ARG, "spslam_track_update_local_map: negative capacity%s", "");
+    if ((n_kp && !m.frame_rows) || !m.obs_off || !m.covis || !m.child_off || !m.parent || !m.match_off ||
+        !o.local_kfs || !o.n_local_kfs || !o.kf_max || !o.n_local || !o.status || (o.capacity && !o.local_rows) ||
+        (o.records && !m.points && n_rows))
+        return fail(c, SPSLAM_ERR_ARG, "missing buffer for spslam_track_update_local_map%s", "");
+    const int nk = m.n_kf, n_obs = m.obs_off[n_rows], n_child = m.child_off[nk], n_match = m.match_off[nk];
+    if (m.obs_off[0] != 0 || m.child_off[0] != 0 || m.match_off[0] != 0 || n_obs < 0 || n_child < 0 || n_match < 0 ||
+        (n_obs && !m.obs_kf) || (n_child && !m.child) || (n_match && !m.match_row) || *o.n_local_kfs < 0 ||
+        *o.n_local_kfs > nk)
+        return fail(c, SPSLAM_ERR_ARG, "spslam_track_update_local_map: a CSR does not start at 0 or lacks its "
+                    "array, or n_local_kfs outside 0 .. n_kf%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const size_t R = (size_t)n_rows, K = (size_t)nk, C = (size_t)o.capacity, P = sizeof(spslam_local_point);
+    const int cap = std::max(n_kp, 1);
+    // {keypoints, base 0, n_local_kfs, kf_max, n_local, status}
+    int32_t hdr[6] = {n_kp, 0, *o.n_local_kfs, -1, 0, 0};
+    spslam_local_frame lf{};
+    const bool with_frame = o.records && o.local_frames;
+    if (with_frame) lf = *o.local_frames;
+    Stage st(c);
+    if (int rc = st.open({{hdr, sizeof hdr},
+                           {m.frame_rows, (size_t)n_kp * 4, (size_t)cap * 4},
+                           {m.obs_off, (R + 1) * 4}, {m.obs_kf, (size_t)n_obs * 4, std::max(n_obs, 1) * (size_t)4},
+                           {m.point_bad, m.point_bad ? R : 0, std::max(R, (size_t)1)},
+                           {m.kf_bad, m.kf_bad ? K : 0, K}, {m.covis, K * 40}, {m.child_off, (K + 1) * 4},
+                           {m.child, (size_t)n_child * 4, std::max(n_child, 1) * (size_t)4}, {m.parent, K * 4},
+                           {m.match_off, (K + 1) * 4},
+                           {m.match_row, (size_t)n_match * 4, std::max(n_match, 1) * (size_t)4},
+                           {m.points, o.records ? R * P : 0, std::max(R, (size_t)1) * P},
+                           {o.local_kfs, (size_t)*o.n_local_kfs * 4, K * 4}, std::max(C, (size_t)1) * 4,
+                           std::max(R, (size_t)1) * 4, std::max(C, (size_t)1) * P, {&lf, sizeof lf}}))
+        return rc;
+    int32_t* d_hdr = st.slot<int32_t>(0);
+    spslam_local_map dm{};
+    dm.frame_rows = st.slot<int32_t>(1);
+    dm.kp_counts = d_hdr;
+    dm.kf_base = dm.row_base = d_hdr + 1;
+    dm.cap = cap;
+    dm.n_kf = nk;
+    dm.obs_off = st.slot<int32_t>(2);
+    dm.obs_kf = st.slot<int32_t>(3);
+    dm.point_bad = m.point_bad ? st.slot<uint8_t>(4) : nullptr;
+    dm.points = st.slot<spslam_local_point>(12);
+    dm.kf_bad = m.kf_bad ? st.slot<uint8_t>(5) : nullptr;
+    dm.covis = st.slot<int32_t>(6);
+    dm.child_off = st.slot<int32_t>(7);
+    dm.child = st.slot<int32_t>(8);
+    dm.parent = st.slot<int32_t>(9);
+    dm.match_off = st.slot<int32_t>(10);
+    dm.match_row = st.slot<int32_t>(11);
+    spslam_local_map_out dout{};
+    dout.local_kfs = st.slot<int32_t>(13);
+    dout.n_local_kfs = d_hdr + 2;
+    dout.kf_max = d_hdr + 3;
+    dout.n_local = d_hdr + 4;
+    dout.status = d_hdr + 5;
+    dout.local_rows = st.slot<int32_t>(14);
+    dout.scratch = st.slot<int32_t>(15);  // deliberately not cleared: the kernel does not read what it held
+    dout.kf_cap = nk;
+    dout.capacity = o.capacity;
+    dout.scratch_stride = n_rows;
+    dout.records = o.records ? st.slot<spslam_local_point>(16) : nullptr;
+    dout.local_frames = with_frame ? st.slot<spslam_local_frame>(17) : nullptr;
+    int rc = spslam_track_update_local_map_batch_device(c, 1, nullptr, &dm, &dout, c->stream);
+    if (rc) return rc;
+    HIP_CHECK(c, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    *o.n_local_kfs = hdr[2];
+    *o.kf_max = hdr[3];
+    *o.n_local = hdr[4];
+    *o.status = hdr[5];
+    if (hdr[2]) HIP_CHECK(c, hipMemcpyAsync(o.local_kfs, dout.local_kfs, (size_t)hdr[2] * 4, hipMemcpyDeviceToHost, c->stream));
+    if (hdr[4]) {
+        HIP_CHECK(c, hipMemcpyAsync(o.local_rows, dout.local_rows, (size_t)hdr[4] * 4, hipMemcpyDeviceToHost, c->stream));
+        if (o.records)
+            HIP_CHECK(c, hipMemcpyAsync(o.records, dout.records, (size_t)hdr[4] * P, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (with_frame)
+        HIP_CHECK(c, hipMemcpyAsync(o.local_frames, dout.local_frames, sizeof lf, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
 int spslam_masked_frame_copy_device(spslam_ctx* c, int n_frames, const uint8_t* flags, int n_regions,
                                     const spslam_frame_region* regions, void* hip_stream) {
     if (!c) return SPSLAM_ERR_ARG;

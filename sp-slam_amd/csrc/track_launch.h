@@ -21,6 +21,11 @@ hipError_t refkf_vote_launch(int n_frames, const spslam_track_batch& mm, const s
 hipError_t refkf_launch(int n_frames, int stage, const spslam_track_batch& mm, const spslam_refkf_batch& rk,
                         hipStream_t s);
 
+// Tracking::UpdateLocalMap per frame (local_map_kernels.hip, spslam_track_update_local_map_batch_device); mm may be
+// null when map.frame_rows is given.  Timed under the tracking kind.
+hipError_t update_local_map_launch(int n_frames, const spslam_track_batch* mm, const spslam_local_map& map,
+                                   const spslam_local_map_out& out, hipStream_t s, KernelTimer* timer);
+
 constexpr int kMaxFrameRegions = 32;
 struct FrameRegions {
     spslam_frame_region r[kMaxFrameRegions];

@@ -74,6 +74,7 @@ class SeqMap:
         self.obs = {}          # pid -> {j: kp}
         self.ref = {}          # pid -> reference keyframe (the one that created it)
         self.plane_obs = {}    # plane row -> {kind: {j: meas}}
+        self.parent = {}       # j -> spanning-tree parent (first-connection rule, insert_keyframe)
 
     # ---- keyframe insertion
     def insert_keyframe(self, j, Tcw, keys_un, uright, octave, matched, plane_edges):
@@ -100,6 +101,10 @@ class SeqMap:
             kf["planes"].append((int(kind), r))
             self.plane_obs.setdefault(r, {}).setdefault(int(kind), {})[j] = np.asarray(meas, np.float32).copy()
         self.kfs[j] = kf
+        # KeyFrame::UpdateConnections' first connection (KeyFrame.cc:388-392): the parent is the front of the
+        # ordered covisibles when the keyframe is inserted, never for keyframe 0; none while it shares no point
+        cov = self.covisible(j) if j != 0 else []
+        self.parent[j] = cov[0] if cov else -1
 
     def covisible(self, j):
         """KeyFrame::UpdateConnections + GetVectorCovisibleKeyFrames: keyframes sharing >= 15 map points with j
@@ -302,6 +307,41 @@ class SeqMap:
         j = (t - 1) // synth.KEYFRAME_STEP
         a = self.kf_rows[max(j - 1, 0)][0]
         return self.table[a:self.kf_rows[j][1]]
+
+    def local_map_tables(self):
+        """The sequence's map as the tables of struct spslam_local_map (include/spslam_gpu.h; Tracking::
+        UpdateLocalMap, Tracking.cc:1427-1571), indices local to the sequence: per table row the observer CSR
+        (obs, keyframes ascending); per keyframe the 10 best covisibles (covisible(j), -1 padded), the children
+        CSR (ascending) and the parent recorded at insertion, and the map-point-match CSR in keypoint order (row
+        or -1).  No bad flags: this model has none."""
+        nk, nr = max(self.kfs) + 1, len(self.table)
+        obs_off, obs_kf = np.zeros(nr + 1, np.int32), []
+        for r, pid in enumerate(self.table["id"].tolist()):
+            obs_kf.extend(sorted(self.obs.get(pid, {})))
+            obs_off[r + 1] = len(obs_kf)
+        covis = np.full((nk, 10), -1, np.int32)
+        parent = np.full(nk, -1, np.int32)
+        children = [[] for _ in range(nk)]
+        match_off, match_row = np.zeros(nk + 1, np.int32), []
+        for j in range(nk):
+            kf = self.kfs.get(j)
+            if kf is not None:
+                c = self.covisible(j)[:10]
+                covis[j, :len(c)] = c
+                parent[j] = self.parent.get(j, -1)
+                if parent[j] >= 0:
+                    children[parent[j]].append(j)
+                rows = np.full(len(kf["ur"]), -1, np.int32)
+                for kp, pid in kf["mp"].items():
+                    rows[kp] = self.row_of[pid]
+                match_row.append(rows)
+            match_off[j + 1] = match_off[j] + (len(match_row[-1]) if kf is not None else 0)
+        child_off = np.zeros(nk + 1, np.int32)
+        child_off[1:] = np.cumsum([len(c) for c in children])
+        return dict(obs_off=obs_off, obs_kf=np.asarray(obs_kf, np.int32), point_bad=np.zeros(nr, np.uint8),
+                    kf_bad=np.zeros(nk, np.uint8), covis=covis, child_off=child_off,
+                    child=np.asarray([c for cs in children for c in cs], np.int32), parent=parent,
+                    match_off=match_off, match_row=np.concatenate(match_row) if match_row else np.zeros(0, np.int32))
 
     def refresh_last_frame(self, P):
         """The last frame's map points after the write-back: positions from the table (by id)."""
