@@ -275,9 +275,13 @@ typedef struct spslam_lba_result {
     int32_t stopped;          /* pbStopFlag: 0 not seen (or seen after the schedule ended), 1 seen before
                                  optimize(5) -- returned, outputs = inputs, no outliers -- 2 seen at a later
                                  check point: the schedule ended there (trials = trials run) */
-    int32_t pad;
-    float phase_us[8];        /* diagnostics: device time per phase (setup, errors, edge terms, block sums,
-                                 Schur, factorisation, substitution, update), microseconds */
+    int32_t pad;              /* diagnostics (g2o order: the sums part of buildSystem, microseconds; else 0) */
+    float phase_us[8];        /* diagnostics, device microseconds.  g2o order: [0] the whole call (kernel start
+                                 to outputs), then the leader's time per phase: [1] setup, structure, update
+                                 and the LM decisions, [2] errors, [3] the ordered chi2 / scale sums,
+                                 [4] buildSystem (edge terms and block sums), [5] Schur, [6] factorisation
+                                 and solve, [7] unused (0).  Fast order: [0] setup to outputs, [1..7] 0.
+                                 Diagnostic builds (SPSLAM_LBG_DIAG*) put other figures in [1..7] and pad. */
 } spslam_lba_result;
 
 /* Drop-in for Optimizer::LocalBundleAdjustment on host buffers, one problem

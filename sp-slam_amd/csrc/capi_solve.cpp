@@ -15,29 +15,14 @@ int lba_rows_max_team() {
     return v;
 }
 
-// the device arrays of one LBA batch
-struct LbaIo {
-    const spslam_lba_problem* probs;
-    const spslam_lba_keyframe* kfs;
-    const spslam_lba_point* pts;
-    const spslam_lba_point_obs* pobs;
-    const spslam_lba_plane* pls;
-    const spslam_lba_plane_obs* plobs;
-    float *kf_out, *pt_out, *pl_out;
-    uint8_t *pobs_out, *plobs_out;
-    spslam_lba_result* res;
-    const int32_t* stop;
-};
-
 // g2o order: one launch runs every problem's whole schedule
 int lba_g2o_order(spslam_ctx* c, int n, const LbaIo& io, const LbaConsts& C, int pw, hipStream_t s) {
     HIP_CHECK(c, c->d_lba_ctl.reserve(lbg_ctl_ints(n) * sizeof(int), s));
     // workgroups per problem: the context's setting, else as many as fill the chip's CUs (one each), at most 8
     int team = c->lba_team;
     if (team <= 0) team = std::max(1, std::min(8, c->num_cus / n));
-    LbgBatch B{n, io.probs, c->d_lba_off, c->d_lba_scratch, io.kfs, io.pts, io.pobs, io.pls, io.plobs,
-               io.kf_out, io.pt_out, io.pl_out, io.pobs_out, io.plobs_out, io.res, io.stop,
-               c->lba_stop_after, team, c->solve_fail_mask, c->d_lba_ctl, pw, lba_rows_max_team()};
+    LbgBatch B{n, c->d_lba_off, c->d_lba_scratch, io, c->lba_stop_after, team, c->solve_fail_mask, c->d_lba_ctl, pw,
+               lba_rows_max_team()};
     HIP_CHECK(c, lba_run_g2o(B, C, s, c->timer));
     return SPSLAM_OK;
 }
@@ -100,9 +85,7 @@ int lba_fast_order(spslam_ctx* c, int n, const spslam_lba_problem* problems, con
     HIP_CHECK(c, hipMemcpyAsync(c->d_lba_work, work.data(), work.size() * sizeof(int2), hipMemcpyHostToDevice, s));
     LbaWork W{w[0], (int)ec.size(), w[1], (int)lc.size(), w[2], (int)kt.size(), w[3], (int)pt.size(),
               w[4], (int)qt.size(), w[5], (int)sg.size(), w[6], (int)pm.size(), seg_own};
-    LbaBatch B{n, io.probs, c->d_lba_off, c->d_lba_scratch, io.kfs, io.pts, io.pobs, io.pls, io.plobs,
-               io.kf_out, io.pt_out, io.pl_out, io.pobs_out, io.plobs_out, io.res,
-               (int*)(c->d_lba_work + work.size() - 1), io.stop, c->lba_stop_after};
+    LbaBatch B{n, c->d_lba_off, c->d_lba_scratch, io, (int*)(c->d_lba_work + work.size() - 1), c->lba_stop_after};
     // optimize(5) + optimize(10), at most 10 trials per iteration, plus the two structure steps
     HIP_CHECK(c, lba_run(B, W, C, 15 * 10 + 4, s, c->timer, nullptr, stop_src, stop_mirror));
     return SPSLAM_OK;

@@ -1,6 +1,6 @@
 // g2o / Eigen / g2oAddition math on the device (fp64), shared by the
 // PoseOptimization (pose_kernels.hip) and LocalBundleAdjustment
-// (lba_kernels.hip) kernels: SE3Quat (Thirdparty/g2o/g2o/types/se3quat.h),
+// (lba_g2o.hip, lba_kernels.hip) kernels: the Huber kernel, SE3Quat (Thirdparty/g2o/g2o/types/se3quat.h),
 // Eigen quaternion / rotation conversions, g2oAddition/Plane3D.h.
 // See oracle/g2o_restated.h for the CPU restatement of the same routines.
 // sin / cos / atan2 / pow(x, 3) are correctly rounded (libm64_cr.h, the path's pinned libm semantics,
@@ -146,6 +146,15 @@ __device__ __forceinline__ SE3 se3_exp(const double* u) {
     s.t = mv(V, ups);
     q_normalize(s.r);
     return s;
+}
+
+// RobustKernelHuber::robustify: rho0 (the robustified chi2) and rho1 (its derivative); off: chi2, 1
+__device__ __forceinline__ void huber(double chi, double delta, bool on, double* rho0, double* rho1) {
+    const double dsqr = delta * delta;
+    if (!on || chi <= dsqr) { *rho0 = chi; *rho1 = 1.0; return; }
+    const double s = sqrt(chi);
+    *rho0 = 2 * s * delta - dsqr;
+    *rho1 = delta / s;
 }
 
 // ---- g2oAddition/Plane3D.h ------------------------------------------------

@@ -38,12 +38,14 @@
 #include <cfloat>
 
 #include "g2o_device.h"
+#include "lba_edge_math.h"
 #include "lba_launch.h"
 
 namespace spslam {
 namespace lba {
 
 using namespace g2od;
+using namespace edge_math;
 
 constexpr int kThreads = kLbaChunk, kWaves = kThreads / 64;
 constexpr int kStruct = 0, kIter = 1, kTrial = 2, kRelabel = 3, kDone = 4;
@@ -65,13 +67,13 @@ struct Ctx {
 };
 
 __device__ Ctx make_ctx(const LbaBatch& b, int p) {
-    const spslam_lba_problem pb = b.probs[p];
+    const spslam_lba_problem pb = b.io.probs[p];
     Ctx c;
     c.K = pb.n_kf; c.Np = pb.n_points; c.Nq = pb.n_planes;
     c.Ep = pb.n_point_obs; c.E = pb.n_point_obs + pb.n_plane_obs; c.L = c.Np + c.Nq;
     c.nEc = lba_chunks(c.E); c.nLc = lba_chunks(c.L);
-    c.kf = b.kfs + pb.kf_offset; c.pt = b.pts + pb.point_offset; c.pl = b.pls + pb.plane_offset;
-    c.pobs = b.pobs; c.plobs = b.plobs;
+    c.kf = b.io.kfs + pb.kf_offset; c.pt = b.io.pts + pb.point_offset; c.pl = b.io.pls + pb.plane_offset;
+    c.pobs = b.io.pobs; c.plobs = b.io.plobs;
     const LbaLayout Ly = lba_layout(c.K, c.Np, c.Nq, c.E);
     uint8_t* base = b.scratch + b.scratch_off[p];
     c.ctl = (LbaCtl*)(base + Ly.ctl);
@@ -102,110 +104,41 @@ __device__ __forceinline__ void wave_sync() {  // LDS written by this wave, visi
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ SE3 load_pose(const double* p) { return SE3{Q{p[0], p[1], p[2], p[3]}, V3{p[4], p[5], p[6]}}; }
-__device__ __forceinline__ void store_pose(double* p, const SE3& T) {
-    p[0] = T.r.w; p[1] = T.r.x; p[2] = T.r.y; p[3] = T.r.z; p[4] = T.t.x; p[5] = T.t.y; p[6] = T.t.z;
-}
 // SparseOptimizer::terminate(): the caller's flag, read through to memory (it may be host-coherent and
 // raised by another thread while the schedule runs), latched once seen
 __device__ __forceinline__ bool stop_requested(const LbaBatch& b, int p, LbaCtl& k) {
-    if (!k.stop && b.stop) k.stop = __hip_atomic_load(b.stop + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
+    if (!k.stop && b.io.stop) k.stop = __hip_atomic_load(b.io.stop + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
     if (!k.stop && b.stop_after >= 0 && k.trials >= b.stop_after) k.stop = 1;  // spslam_lba_debug_stop_after
     return k.stop != 0;
 }
 
-// Converter::toPlane3D (flip d < 0) + Plane3D(v) normalisation
-__device__ __forceinline__ P4 plane_from_f(const float* c) {
-    P4 p{{c[0], c[1], c[2], c[3]}};
-    if (c[3] < 0.0f)
-        for (int i = 0; i < 4; i++) p.c[i] = -p.c[i];
-    p_normalize(p.c);
-    return p;
-}
-// operator*(Isometry3D, Plane3D)
-__device__ P4 plane_transform(const SE3& T, const P4& w) {
-    const M3 R = q_to_rot(T.r);
-    const V3 n2 = mv(R, V3{w.c[0], w.c[1], w.c[2]});
-    P4 v{{n2.x, n2.y, n2.z, w.c[3] - dot(T.t, n2)}};
-    if (v.c[3] < 0.0)
-        for (int i = 0; i < 4; i++) v.c[i] = -v.c[i];
-    p_normalize(v.c);
-    return v;
-}
-// (T * world).ominus{,_par,_ver}(meas) for edge types 2 / 3 / 4
-__device__ void plane_edge_error(int type, const SE3& T, const P4& world, const P4& meas, double* e) {
-    plane_error(type - 2, T, world, meas, e);
-}
-
-__device__ __forceinline__ int edge_dim(int type) { return type == 0 ? 2 : (type == 1 || type == 2) ? 3 : 2; }
-
-__device__ void info_of(const Ctx& c, const LbaConsts& C, int e, double* info) {
+__device__ __forceinline__ void info_of(const Ctx& c, const LbaConsts& C, int e, double* info) {
     const int t = c.e_type[e];
-    if (t <= 1) {
-        const double s = (double)c.pobs[c.e_src[e]].inv_sigma2;
-        info[0] = info[1] = info[2] = s;
-    } else if (t == 2) {
-        info[0] = info[1] = C.angle_info; info[2] = C.dis_info;
-    } else {
-        info[0] = info[1] = t == 3 ? C.par_info : C.ver_info;
-        info[2] = 0;
-    }
+    edge_math::info_of(C, t, t <= 1 ? c.pobs[c.e_src[e]].inv_sigma2 : 0.0f, info);
 }
-
-__device__ void edge_error(const Ctx& c, int e, const SE3& T, const double* X, const P4* P, double* err) {
-    const int t = c.e_type[e];
-    if (t <= 1) {
-        const spslam_lba_point_obs& o = c.pobs[c.e_src[e]];
-        const spslam_lba_keyframe& k = c.kf[c.e_kf[e]];
-        const V3 p = q_rot(T.r, V3{X[0], X[1], X[2]}) + T.t;
-        if (t == 0) {
-            err[0] = (double)o.u - (p.x / p.z * (double)k.fx + (double)k.cx);
-            err[1] = (double)o.v - (p.y / p.z * (double)k.fy + (double)k.cy);
-        } else {
-            const float invz = (float)(1.0f / p.z);
-            const double r0 = p.x * invz * (double)k.fx + (double)k.cx, r1 = p.y * invz * (double)k.fy + (double)k.cy;
-            const double r2 = r0 - (double)(k.bf * invz);  // cam_project(..., const float& bf)
-            err[0] = (double)o.u - r0;
-            err[1] = (double)o.v - r1;
-            err[2] = (double)o.ur - r2;
-        }
-        return;
-    }
-    plane_edge_error(t, T, *P, plane_from_f(c.plobs[c.e_src[e]].meas), err);
+__device__ __forceinline__ PointIn point_in(const Ctx& c, int e) {
+    const int kf = c.e_kf[e], lm = c.e_lm[e];
+    PointIn a;
+    a.T = load_pose(c.pose + 7 * kf);
+    for (int i = 0; i < 3; i++) a.X[i] = c.X[3 * lm + i];
+    const spslam_lba_point_obs& o = c.pobs[c.e_src[e]];
+    a.u = o.u; a.v = o.v; a.ur = o.ur; a.isg = o.inv_sigma2;
+    const spslam_lba_keyframe& k = c.kf[kf];
+    a.fx = k.fx; a.fy = k.fy; a.cx = k.cx; a.cy = k.cy; a.bf = k.bf;
+    return a;
 }
-
-__device__ __forceinline__ const double* lm_state(const Ctx& c, int lm) {
-    return lm < c.Np ? c.X + 3 * lm : c.P + 4 * (lm - c.Np);
-}
+// Not edge_math::chi2_of, on purpose: (e[i] info[i]) e[i] here, e[i] (info[i] e[i]) there; they round differently
 __device__ __forceinline__ double chi2_of(const double* err, const double* info, int dim) {
     double s = 0;
     for (int i = 0; i < dim; i++) s += err[i] * info[i] * err[i];
     return s;
 }
-__device__ __forceinline__ void huber(double chi, double delta, bool on, double* rho0, double* rho1) {
-    const double dsqr = delta * delta;
-    if (!on || chi <= dsqr) { *rho0 = chi; *rho1 = 1.0; return; }
-    const double s = sqrt(chi);
-    *rho0 = 2 * s * delta - dsqr;
-    *rho1 = delta / s;
-}
-__device__ __forceinline__ double delta_of(const LbaConsts& C, int t) {
-    return t == 0 ? C.delta_mono : t == 1 ? C.delta_stereo : t == 2 ? C.delta_plane : C.delta_vp;
-}
-
 __device__ bool depth_positive(const Ctx& c, int e) {
     const SE3 T = load_pose(c.pose + 7 * c.e_kf[e]);
     const int lm = c.e_lm[e];
-    if (c.e_type[e] <= 1) {
-        const double* X = c.X + 3 * lm;
-        return (q_rot(T.r, V3{X[0], X[1], X[2]}) + T.t).z > 0.0;
-    }
-    const double* pp = c.P + 4 * (lm - c.Np);
-    const P4 w{{pp[0], pp[1], pp[2], pp[3]}};
-    return -plane_transform(T, w).c[3] > 0;
+    if (c.e_type[e] <= 1) return edge_math::depth_positive(T, true, c.X + 3 * lm);
+    return edge_math::depth_positive(T, false, c.P + 4 * (lm - c.Np));
 }
-
-// Block-wide sum of NV doubles per thread; result valid in every thread.
 
 struct Red {
     double v[kWaves][40];
@@ -233,37 +166,6 @@ __device__ void block_sum(double (&v)[NV], Red& R) {
     }
     __syncthreads();
 }
-__device__ double block_max(double v, Red& R) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    if (lane == 0) R.v[w][0] = v;
-    __syncthreads();
-    double m = 0;
-    for (int j = 0; j < kWaves; j++) m = fmax(m, R.v[j][0]);
-    __syncthreads();
-    return m;
-}
-// Exclusive block scan of one int per thread; *total = block sum.
-__device__ int block_scan(int v, int* total, Red& R) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) R.wsum[w] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int j = 0; j < kWaves; j++) {
-        if (j < w) base += R.wsum[j];
-        tot += R.wsum[j];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
 
 __device__ __forceinline__ int lm_block_base(const Ctx& c, int l) { return c.lm_act[l] - 1; }
 // e_blk: the edge's (landmark, pose) block, -1 if none; kBlkShared marks the edges of a landmark with two active
@@ -274,96 +176,12 @@ __device__ __forceinline__ int edge_block(const Ctx& c, int e) {
     return v < 0 ? -1 : (v & (kBlkShared - 1));
 }
 
-// Edge Jacobians: A (landmark, dim x 3), B (pose, dim x 6); fixed vertices skipped.
-// kOnly: 0 = any edge, 1 = point edges only, 2 = plane edges only (the caller filtered the type; instances
-// without the numeric plane Jacobians need far fewer registers)
-template <int kOnly = 0>
-__device__ void edge_jacobians(const Ctx& c, int e, bool pose_free, double (&A)[3][3], double (&B)[3][6]) {
-    const int t = c.e_type[e], lm = c.e_lm[e];
-    const SE3 T = load_pose(c.pose + 7 * c.e_kf[e]);
-    if (kOnly != 2 && (kOnly == 1 || t <= 1)) {
-        const spslam_lba_keyframe& k = c.kf[c.e_kf[e]];
-        const double fx = k.fx, fy = k.fy, bf = k.bf;
-        const double* X = c.X + 3 * lm;
-        const V3 p = q_rot(T.r, V3{X[0], X[1], X[2]}) + T.t;
-        const double x = p.x, y = p.y, z = p.z, z_2 = z * z;
-        const M3 R = q_to_rot(T.r);
-        if (t == 0) {
-            const double tmp[2][3] = {{fx, 0, -x / z * fx}, {0, fy, -y / z * fy}};
-            const double s = -1. / z;
-            for (int r = 0; r < 2; r++) {
-                const double t0 = s * tmp[r][0], t1 = s * tmp[r][1], t2 = s * tmp[r][2];
-                for (int q = 0; q < 3; q++) A[r][q] = t0 * R.a[q] + t1 * R.a[3 + q] + t2 * R.a[6 + q];
-            }
-        } else {
-            for (int q = 0; q < 3; q++) {
-                A[0][q] = -fx * R.a[q] / z + fx * x * R.a[6 + q] / z_2;
-                A[1][q] = -fy * R.a[3 + q] / z + fy * y * R.a[6 + q] / z_2;
-                A[2][q] = A[0][q] - bf * R.a[6 + q] / z_2;
-            }
-        }
-        B[0][0] = x * y / z_2 * fx; B[0][1] = -(1 + (x * x / z_2)) * fx; B[0][2] = y / z * fx;
-        B[0][3] = -1. / z * fx; B[0][4] = 0; B[0][5] = x / z_2 * fx;
-        B[1][0] = (1 + y * y / z_2) * fy; B[1][1] = -x * y / z_2 * fy; B[1][2] = -x / z * fy;
-        B[1][3] = 0; B[1][4] = -1. / z * fy; B[1][5] = y / z_2 * fy;
-        if (t == 1) {
-            B[2][0] = B[0][0] - bf * y / z_2; B[2][1] = B[0][1] + bf * x / z_2; B[2][2] = B[0][2];
-            B[2][3] = B[0][3]; B[2][4] = 0; B[2][5] = B[0][5] - bf / z_2;
-        }
-        return;
-    }
-    const double delta = 1e-9, scalar = 1.0 / (2 * delta);
-    const double* pp = c.P + 4 * (lm - c.Np);
-    const P4 P0{{pp[0], pp[1], pp[2], pp[3]}};
-    const P4 meas = plane_from_f(c.plobs[c.e_src[e]].meas);
-    const int dim = edge_dim(t);
-    double ep[3], em[3];
-    for (int d = 0; d < 3; d++) {
-        double add[3] = {0, 0, 0};
-        add[d] = delta;
-        P4 P = P0;
-        p_oplus(P, add);
-        plane_edge_error(t, T, P, meas, ep);
-        add[d] = -delta;
-        P = P0;
-        p_oplus(P, add);
-        plane_edge_error(t, T, P, meas, em);
-#pragma unroll
-        for (int i = 0; i < 3; i++) A[i][d] = i < dim ? scalar * (ep[i] - em[i]) : 0.0;
-    }
-    if (!pose_free) return;
-    for (int d = 0; d < 6; d++) {
-        double add[6] = {0, 0, 0, 0, 0, 0};
-        add[d] = delta;
-        plane_edge_error(t, se3_mul(se3_exp(add), T), P0, meas, ep);
-        add[d] = -delta;
-        plane_edge_error(t, se3_mul(se3_exp(add), T), P0, meas, em);
-#pragma unroll
-        for (int i = 0; i < 3; i++) B[i][d] = i < dim ? scalar * (ep[i] - em[i]) : 0.0;
-    }
-}
-
-// Eigen compute_inverse<Matrix3d>
-__device__ void inverse3(const double (&m)[3][3], double* r) {
-    auto cof = [&](int i, int j) {
-        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-        return m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1];
-    };
-    const double c0 = cof(0, 0), c1 = cof(1, 0), c2 = cof(2, 0);
-    const double det = (c0 * m[0][0] + c1 * m[1][0]) + c2 * m[2][0];
-    const double invdet = 1.0 / det;
-    r[0] = c0 * invdet; r[1] = c1 * invdet; r[2] = c2 * invdet;
-    r[3] = cof(0, 1) * invdet; r[4] = cof(1, 1) * invdet; r[5] = cof(2, 1) * invdet;
-    r[6] = cof(0, 2) * invdet; r[7] = cof(1, 2) * invdet; r[8] = cof(2, 2) * invdet;
-}
-
-
 // ---------------------------------------------------------------- setup
 __global__ __launch_bounds__(kThreads) void k_setup(LbaBatch b, int max_it0) {
     __shared__ Red R;
     const int p = blockIdx.x, t = threadIdx.x;
     Ctx c = make_ctx(b, p);
-    spslam_lba_result* res = b.res + p;
+    spslam_lba_result* res = b.io.res + p;
     if (c.K > kLbaMaxKeyframes) {
         if (t == 0) {
             *res = spslam_lba_result{};
@@ -395,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void k_setup(LbaBatch b, int max_it0) {
         const int l = ch + t;
         const int n_obs = l < c.Np ? c.pt[l].n_obs : (l < c.L ? c.pl[l - c.Np].n_obs : 0);
         int tot;
-        const int off = block_scan(n_obs, &tot, R) + base_e;
+        const int off = block_scan(n_obs, &tot, R.wsum) + base_e;
         if (l < c.L) {
             c.lm_boff[l] = off;
             c.lm_nb[l] = n_obs;
@@ -455,7 +273,7 @@ __global__ __launch_bounds__(kThreads) void k_struct_count(LbaBatch b, LbaWork w
     int n = 0;
     for (int e = threadIdx.x; e < c.E; e += kThreads) n += (c.e_level[e] == 0 && c.e_kf[e] == k);
     int tot;
-    block_scan(n, &tot, R);
+    block_scan(n, &tot, R.wsum);
     if (threadIdx.x == 0) c.kf_cnt[k] = tot;
 }
 
@@ -507,7 +325,7 @@ __global__ __launch_bounds__(kThreads) void k_struct_final(LbaBatch b) {
             }
         const int nb = __popcll(mask);
         int tot;
-        const int off = block_scan(nb, &tot, R) + base;
+        const int off = block_scan(nb, &tot, R.wsum) + base;
         if (l < c.L) {
             c.lm_mask[l] = mask;
             c.lm_act[l] = act ? off + 1 : 0;
@@ -534,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void k_struct_fill(LbaBatch b, LbaWork w)
         const int e = ch + threadIdx.x;
         const int f = e < c.E && c.e_level[e] == 0 && c.e_kf[e] == k;
         int tot;
-        const int r = block_scan(f, &tot, R);
+        const int r = block_scan(f, &tot, R.wsum);
         if (f) c.pe_idx[o + r] = e;
         o += tot;
     }
@@ -563,18 +381,17 @@ __global__ __launch_bounds__(kThreads) void k_errors(LbaBatch b, LbaWork w, LbaC
     const int e = task.y + threadIdx.x;
     double acc[1] = {0.0};
     if (e < c.E && c.e_level[e] == 0) {
-        const int lm = c.e_lm[e];
-        const SE3 T = load_pose(c.pose + 7 * c.e_kf[e]);
+        const int ty = c.e_type[e];
         double* err = c.err + 3 * e;
-        P4 P;
-        if (lm >= c.Np) {
-            const double* pp = c.P + 4 * (lm - c.Np);
-            P = P4{{pp[0], pp[1], pp[2], pp[3]}};
+        if (ty <= 1) {
+            point_edge_error(ty, point_in(c, e), err);
+        } else {  // (T * world).ominus{,_par,_ver}(meas) for edge types 2 / 3 / 4
+            const double* pp = c.P + 4 * (c.e_lm[e] - c.Np);
+            plane_error(ty - 2, load_pose(c.pose + 7 * c.e_kf[e]), P4{{pp[0], pp[1], pp[2], pp[3]}},
+                        plane_from_f(c.plobs[c.e_src[e]].meas), err);
         }
-        edge_error(c, e, T, lm < c.Np ? c.X + 3 * lm : nullptr, &P, err);
         double info[3];
         info_of(c, C, e, info);
-        const int ty = c.e_type[e];
         double r0, r1;
         huber(chi2_of(err, info, edge_dim(ty)), delta_of(C, ty), k.robust, &r0, &r1);
         acc[0] = r0;
@@ -687,7 +504,7 @@ __global__ __launch_bounds__(kThreads, SPSLAM_LBA_PL_WAVES) void k_plane_terms(L
 
 // Point edges and point landmarks in one pass (the point part of k_lm_sums, without a per-edge kernel before
 // it): a workgroup computes the quadratic-form terms of 256 consecutive point edges, one edge per thread
-// (edge_jacobians<1> and store_terms' formulas).  Each edge's (landmark, pose) block (Hpl, 18) goes straight to
+// (point_edge_jacobians and store_terms' formulas). Each edge's (landmark, pose) block (Hpl, 18) goes straight to
 // memory from its thread -- the block's only term -- and its landmark terms (Hll 9, bl 3) to LDS; a landmark's
 // edges are consecutive and at most kLbaMaxKeyframes, so the workgroup owns the landmarks whose first edge lies
 // in its first w.seg_own edges and finds all their edges in LDS (the remaining rows are the halo).  Each owned
@@ -712,8 +529,10 @@ __global__ __launch_bounds__(kThreads, SPSLAM_LBA_PT_WAVES) void k_point_terms_s
     auto land_terms = [&](int ee, double* row, bool own, bool full) __attribute__((always_inline)) {
         const int ty = c.e_type[ee];
         const bool pfree = c.pose_hidx[c.e_kf[ee]] >= 0;
-        double A[3][3] = {}, B[3][6] = {};
-        edge_jacobians<1>(c, ee, pfree, A, B);
+        double A[3][3], B[3][6];
+        const SE3 T = load_pose(c.pose + 7 * c.e_kf[ee]);
+        const spslam_lba_keyframe& cam = c.kf[c.e_kf[ee]];
+        point_edge_jacobians(ty, T, cam.fx, cam.fy, cam.bf, c.X + 3 * c.e_lm[ee], A, B);
         const int dim = edge_dim(ty);
         double info[3];
         info_of(c, C, ee, info);
@@ -812,7 +631,7 @@ __global__ __launch_bounds__(kThreads, SPSLAM_LBA_PT_WAVES) void k_point_terms_s
         for (int j = 0; j < 3; j++) c.lmb[3 * l + j] = bl[j];
         mx = fmax(fabs(H[0]), fmax(fabs(H[4]), fabs(H[8])));
     }
-    mx = block_max(mx, R);
+    mx = block_max(mx, R.v);
     // max |diag| (computeLambdaInit): non-negative doubles order like their bit patterns; k_errors cleared the slot
     if (t == 0 && mx > 0.0) atomicMax((unsigned long long*)c.part_max, (unsigned long long)__double_as_longlong(mx));
 }
@@ -849,7 +668,7 @@ __global__ __launch_bounds__(kThreads) void k_plane_lm_sums(LbaBatch b, LbaWork 
     }
     const double d0 = __shfl(acc, 0), d4 = __shfl(acc, 4), d8 = __shfl(acc, 8);
     double mx = have && lane == 0 ? fmax(fabs(d0), fmax(fabs(d4), fabs(d8))) : 0.0;
-    mx = block_max(mx, R);
+    mx = block_max(mx, R.v);
     if (threadIdx.x == 0 && mx > 0.0)
         atomicMax((unsigned long long*)c.part_max, (unsigned long long)__double_as_longlong(mx));
 }
@@ -1598,18 +1417,18 @@ __global__ __launch_bounds__(kThreads) void k_outputs(LbaBatch b, LbaConsts C) {
     __shared__ Red R;
     const int p = blockIdx.x, t = threadIdx.x;
     Ctx c = make_ctx(b, p);
-    const spslam_lba_problem pb = b.probs[p];
+    const spslam_lba_problem pb = b.io.probs[p];
     if (c.K > kLbaMaxKeyframes) return;
     if (c.ctl->stopped == 1) {  // returned before optimizing: the map is untouched, nothing is erased
         for (int e = t; e < c.E; e += kThreads) {
-            if (e < c.Ep) b.pobs_out[c.e_src[e]] = 0;
-            else b.plobs_out[c.e_src[e]] = 0;
+            if (e < c.Ep) b.io.pobs_out[c.e_src[e]] = 0;
+            else b.io.plobs_out[c.e_src[e]] = 0;
         }
-        for (int i = t; i < 16 * c.K; i += kThreads) b.kf_out[16 * (size_t)pb.kf_offset + i] = c.kf[i / 16].Tcw[i % 16];
-        for (int i = t; i < 3 * c.Np; i += kThreads) b.pt_out[3 * (size_t)pb.point_offset + i] = c.pt[i / 3].xw[i % 3];
-        for (int i = t; i < 4 * c.Nq; i += kThreads) b.pl_out[4 * (size_t)pb.plane_offset + i] = c.pl[i / 4].world[i % 4];
+        for (int i = t; i < 16 * c.K; i += kThreads) b.io.kf_out[16 * (size_t)pb.kf_offset + i] = c.kf[i / 16].Tcw[i % 16];
+        for (int i = t; i < 3 * c.Np; i += kThreads) b.io.pt_out[3 * (size_t)pb.point_offset + i] = c.pt[i / 3].xw[i % 3];
+        for (int i = t; i < 4 * c.Nq; i += kThreads) b.io.pl_out[4 * (size_t)pb.plane_offset + i] = c.pl[i / 4].world[i % 4];
         if (t == 0) {
-            spslam_lba_result* r = b.res + p;
+            spslam_lba_result* r = b.io.res + p;
             *r = spslam_lba_result{};
             r->stopped = 1;
         }
@@ -1623,18 +1442,18 @@ __global__ __launch_bounds__(kThreads) void k_outputs(LbaBatch b, LbaConsts C) {
         const double chi = chi2_of(c.err + 3 * e, info, edge_dim(ty));
         if (ty <= 1) {
             const bool bad = chi > (ty == 0 ? 5.991 : 7.815) || !depth_positive(c, e);
-            b.pobs_out[c.e_src[e]] = bad;
+            b.io.pobs_out[c.e_src[e]] = bad;
             npo += bad;
         } else {
             const bool bad = ty == 2 ? chi > C.plane_chi : chi > C.vp_chi;
-            b.plobs_out[c.e_src[e]] = bad;
+            b.io.plobs_out[c.e_src[e]] = bad;
             nplo += bad;
         }
     }
     double cnt[2] = {(double)npo, (double)nplo};
     block_sum(cnt, R);
     for (int k = t; k < c.K; k += kThreads) {
-        float* o = b.kf_out + 16 * ((size_t)pb.kf_offset + k);
+        float* o = b.io.kf_out + 16 * ((size_t)pb.kf_offset + k);
         if (c.kf[k].fixed) {
             for (int j = 0; j < 16; j++) o[j] = c.kf[k].Tcw[j];
             continue;
@@ -1647,12 +1466,12 @@ __global__ __launch_bounds__(kThreads) void k_outputs(LbaBatch b, LbaConsts C) {
         o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 1.f;
     }
     for (int i = t; i < c.Np; i += kThreads)
-        for (int j = 0; j < 3; j++) b.pt_out[3 * ((size_t)pb.point_offset + i) + j] = (float)c.X[3 * i + j];
+        for (int j = 0; j < 3; j++) b.io.pt_out[3 * ((size_t)pb.point_offset + i) + j] = (float)c.X[3 * i + j];
     for (int i = t; i < c.Nq; i += kThreads)
-        for (int j = 0; j < 4; j++) b.pl_out[4 * ((size_t)pb.plane_offset + i) + j] = (float)c.P[4 * i + j];
+        for (int j = 0; j < 4; j++) b.io.pl_out[4 * ((size_t)pb.plane_offset + i) + j] = (float)c.P[4 * i + j];
     if (t == 0) {
         const LbaCtl& k = *c.ctl;
-        spslam_lba_result* r = b.res + p;
+        spslam_lba_result* r = b.io.res + p;
         *r = spslam_lba_result{};
         r->iterations[0] = k.its[0];
         r->iterations[1] = k.its[1];
@@ -1680,7 +1499,7 @@ hipError_t lba_run(const LbaBatch& b, const LbaWork& w, const LbaConsts& C, int 
     int steps = 0, active = 1;
     while (steps < max_steps) {
         const int st = steps;
-        if (b.stop) hipLaunchKernelGGL(k_step_begin, dim3(P), dim3(64), 0, s, b);
+        if (b.io.stop) hipLaunchKernelGGL(k_step_begin, dim3(P), dim3(64), 0, s, b);
         hipLaunchKernelGGL(k_struct_count, dim3(w.n_kf_tasks), T, 0, s, b, w);
         hipLaunchKernelGGL(k_struct_final, dim3(P), T, 0, s, b);
         hipLaunchKernelGGL(k_struct_fill, dim3(w.n_kf_tasks), T, 0, s, b, w);

@@ -93,11 +93,9 @@ struct LbaWork {
 inline int lba_seg_own(int max_kf) { return kLbaChunk - (max_kf > 1 ? max_kf - 1 : 0); }
 constexpr int kLbaPlaneEdgesPerTask = kLbaChunk / 64;  // one wave per plane edge
 
-struct LbaBatch {
-    int n;
+// The device arrays of one LBA batch (the arguments of spslam_lba_optimize_batch_device), the same for both orders
+struct LbaIo {
     const spslam_lba_problem* probs;
-    const long long* scratch_off;
-    uint8_t* scratch;
     const spslam_lba_keyframe* kfs;
     const spslam_lba_point* pts;
     const spslam_lba_point_obs* pobs;
@@ -106,9 +104,19 @@ struct LbaBatch {
     float *kf_out, *pt_out, *pl_out;
     uint8_t *pobs_out, *plobs_out;
     spslam_lba_result* res;
-    int* active;      // problems not DONE (polled by the host)
     const int32_t* stop;  // per problem pbStopFlag (device-visible; NULL = no flag)
-    int stop_after;       // test hook: the flag counts as raised once a problem has run this many trials (-1 off)
+};
+
+// Kernel arguments (by value).  In both batch structs `io` follows the scratch fields: every kernel starts by reading
+// scratch_off, scratch and io.probs, and with io leading (those reads 112 bytes apart) the fast order's 51-map call
+// measured 0.8 % slower (profiles/r07/lba_edge_math_split.md).
+struct LbaBatch {
+    int n;
+    const long long* scratch_off;
+    uint8_t* scratch;
+    LbaIo io;
+    int* active;      // problems not DONE (polled by the host)
+    int stop_after;   // test hook: the flag counts as raised once a problem has run this many trials (-1 off)
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -182,18 +190,9 @@ __host__ __device__ inline LbgLayout lbg_layout(int K, int Np, int Nq, int E, in
 }
 struct LbgBatch {
     int n;
-    const spslam_lba_problem* probs;
     const long long* scratch_off;
     uint8_t* scratch;
-    const spslam_lba_keyframe* kfs;
-    const spslam_lba_point* pts;
-    const spslam_lba_point_obs* pobs;
-    const spslam_lba_plane* pls;
-    const spslam_lba_plane_obs* plobs;
-    float *kf_out, *pt_out, *pl_out;
-    uint8_t *pobs_out, *plobs_out;
-    spslam_lba_result* res;
-    const int32_t* stop;  // per problem pbStopFlag (device-visible; NULL = no flag)
+    LbaIo io;
     int stop_after;       // test hook: the flag counts as raised once a problem has run this many trials (-1 off)
     int team;             // workgroups per problem (1 .. kLbgTeamMax); the grid is n * team
     unsigned fail_mask;   // test hook: bit q = LM trial q's solve reports failure (spslam_debug_force_solve_failures)

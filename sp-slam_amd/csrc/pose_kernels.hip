@@ -262,14 +262,6 @@ __device__ __forceinline__ void wg_sum(double (&v)[NV], Sh& S, int& buf) {
     buf ^= 1;
 }
 
-__device__ __forceinline__ void huber(double chi, double delta, bool on, double* rho0, double* rho1) {
-    const double dsqr = delta * delta;
-    if (!on || chi <= dsqr) { *rho0 = chi; *rho1 = 1.0; return; }
-    const double s = sqrt(chi);
-    *rho0 = 2 * s * delta - dsqr;
-    *rho1 = delta / s;
-}
-
 // acc += rows start .. start + cnt - 1 of a ring column (slot = row & (kRows - 1)), one after the other: the
 // reference's order.  The rows are added in contiguous segments (the ring wraps at most once), so every group of 8
 // loads is one base address plus immediate offsets.  Three register groups of 8 rotate: while one group's
