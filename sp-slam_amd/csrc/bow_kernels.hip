@@ -26,17 +26,15 @@
 #include <hip/hip_runtime.h>
 
 #include "bow_launch.h"
+#include "orb_match_device.h"
 
 namespace spslam {
 namespace bow {
 
-constexpr int kThreads = 256;
-constexpr int kHisto = 30, kThLow = 50;
+using namespace orb_match;
 
-__device__ __forceinline__ int hamming(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
+constexpr int kThreads = 256;
+constexpr int kThLow = 50;
 
 __global__ __launch_bounds__(kThreads) void bow_words_kernel(VocabDev V, const uint8_t* __restrict__ desc,
                                                              const int* __restrict__ counts, int cap, int n_frames,
@@ -212,27 +210,6 @@ __global__ __launch_bounds__(kThreads) void bow_vectors_kernel(int cap, int P, i
     }
 }
 
-// ComputeThreeMaxima (src/ORBmatcher.cc:1601-1642)
-__device__ void three_maxima(const int* h, int* i1, int* i2, int* i3) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < kHisto; i++) {
-        const int s = h[i];
-        if (s > max1) {
-            max3 = max2; max2 = max1; max1 = s;
-            ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (s > max2) {
-            max3 = max2; max2 = s;
-            ind3 = ind2; ind2 = i;
-        } else if (s > max3) {
-            max3 = s;
-            ind3 = i;
-        }
-    }
-    if (max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-    else if (max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-    *i1 = ind1; *i2 = ind2; *i3 = ind3;
-}
-
 // (best distance, its first position, second best) of a strided scan, merged across lanes
 struct Best {
     int b1, i1, b2;
@@ -293,7 +270,6 @@ __global__ __launch_bounds__(kThreads) void bow_search_kernel(const int2* __rest
     const uint8_t* has = K.has_point + (size_t)kf * K.cap;
     const spslam_keypoint* kk = K.keys + (size_t)kf * K.cap;
     const spslam_keypoint* fk = F.keys + (size_t)fr * F.cap;
-    const float factor = 1.0f / kHisto;
     int count = 0;
     for (int s = wave; s < n_shared; s += kThreads / 64) {
         const int2 nd = shared_nodes[s];
@@ -317,13 +293,7 @@ __global__ __launch_bounds__(kThreads) void bow_search_kernel(const int2* __rest
             }
             if (b.b1 <= kThLow && (float)b.b1 < __fmul_rn(nn_ratio, (float)b.b2)) {
                 const int jf = ffeat[b.i1];
-                int bn = 0;
-                if (check_ori) {
-                    float rot = __fsub_rn(kk[ikf].angle, fk[jf].angle);
-                    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                    bn = (int)roundf(__fmul_rn(rot, factor));
-                    if (bn == kHisto) bn = 0;
-                }
+                const int bn = check_ori ? rotation_bin(kk[ikf].angle, fk[jf].angle) : 0;
                 if (lane == 0) {
                     match[jf] = ikf;
                     bin[jf] = (signed char)bn;

@@ -40,6 +40,7 @@
 #include "g2o_device.h"
 #include "lba_edge_math.h"
 #include "lba_launch.h"
+#include "wave_ops.h"
 
 namespace spslam {
 namespace lba {
@@ -96,12 +97,6 @@ __device__ Ctx make_ctx(const LbaBatch& b, int p) {
     c.kf_cnt = (int*)(base + Ly.kf_cnt); c.pe_off = (int*)(base + Ly.pe_off); c.pe_idx = (int*)(base + Ly.pe_idx);
     c.lm_mask = (uint64_t*)(base + Ly.lm_mask);
     return c;
-}
-
-__device__ __forceinline__ void wave_sync() {  // LDS written by this wave, visible to this wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // SparseOptimizer::terminate(): the caller's flag, read through to memory (it may be host-coherent and

@@ -28,11 +28,15 @@
 #include "wave_priority.h"
 
 #include "match_launch.h"
+#include "orb_match_device.h"
+#include "wave_ops.h"
 
 namespace spslam {
 namespace match {
 
-constexpr int kThreads = 256, kCols = SPSLAM_GRID_COLS, kRows = SPSLAM_GRID_ROWS, kHisto = 30, kThHigh = 100;
+using namespace orb_match;
+
+constexpr int kThreads = 256, kCols = SPSLAM_GRID_COLS, kRows = SPSLAM_GRID_ROWS, kThHigh = 100;
 constexpr uint32_t kNone = 0xffffffffu;
 // lanes per last-frame point in match_window_kernel: the serial chain of dependent loads (cell bounds,
 // grid index, keypoint, descriptor) per candidate is what the in-step time of the window search is made of
@@ -66,12 +70,6 @@ __device__ __forceinline__ void mat3_mul(const float* T, const float* x, const f
     }
 }
 
-__device__ __forceinline__ int hamming(const uint4& a0, const uint4& a1, const uint8_t* b) {
-    const uint4 b0 = *(const uint4*)b, b1 = *(const uint4*)(b + 16);
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
 // bForward / bBackward of one frame pair (src/ORBmatcher.cc:1336-1349)
 __device__ __forceinline__ void direction(const spslam_proj_frame& F, const MatchGeom& g, bool mono, bool* fwd,
                                           bool* bwd) {
@@ -85,26 +83,112 @@ __device__ __forceinline__ void direction(const spslam_proj_frame& F, const Matc
     *bwd = -tlc[2] > mb && !mono;
 }
 
-// Candidate test of GetFeaturesInArea + the stereo check; returns the key or kNone.
-template <class Win>
-__device__ __forceinline__ uint32_t candidate_key(const Win& w, const MatchCurrent& C, const float* uright,
-                                                  const uint8_t* desc, const spslam_keypoint* kun, int j, int k,
-                                                  const uint4& d0, const uint4& d1, const MatchGeom& g) {
-    const spslam_keypoint kp = kun[k];
-    const bool check = (w.min_level > 0) || (w.max_level >= 0);
+// The current frame's arrays of batch entry f: the grid as CSR (cell offsets, keypoints by position), the
+// undistorted keypoints, their descriptors and right coordinates.
+struct FrameView {
+    const int32_t *GO, *GI;
+    const spslam_keypoint* kun;
+    const uint8_t* desc;
+    const float* uright;
+};
+__device__ __forceinline__ FrameView frame_view(const MatchCurrent& C, int f) {
+    return {C.grid_off + (size_t)f * (kCols * kRows + 1), C.grid_idx + (size_t)f * C.cap,
+            C.kun + (size_t)f * C.cap, C.desc + (size_t)f * C.cap * 32, C.uright + (size_t)f * C.cap};
+}
+
+// GetFeaturesInArea cell range of the window (u, v, r); false: the reference returns no candidates
+__device__ __forceinline__ bool cell_range(float u, float v, float r, const MatchGeom& g, int* x0, int* x1, int* y0,
+                                           int* y1) {
+    *x0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, g.min_x), r), g.ginv_x)));
+    *x1 = min(kCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, g.min_x), r), g.ginv_x)));
+    *y0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, g.min_y), r), g.ginv_y)));
+    *y1 = min(kRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, g.min_y), r), g.ginv_y)));
+    return !(*x0 >= kCols || *x1 < 0 || *y0 >= kRows || *y1 < 0);
+}
+
+// What a window's candidates are tested against: the projection, the radius, the projected right coordinate
+// (mTrackProjXR; ur = fma(-mbf, invz, u)), the octave range and the point's descriptor.
+struct Probe {
+    float u, v, r, ur;
+    int min_level, max_level;
+    uint4 d0, d1;
+};
+template <int K>
+__device__ __forceinline__ Probe probe_of(const MatchWindowK<K>& w, const MatchGeom& g, const uint8_t* desc) {
+    return {w.u, w.v, w.r, __fmaf_rn(-g.bf, w.invzc, w.u), w.min_level, w.max_level,
+            *(const uint4*)desc, *(const uint4*)(desc + 16)};
+}
+template <int K>
+__device__ __forceinline__ Probe probe_of(const LocalWindowK<K>& w, const uint8_t* desc) {
+    return {w.u, w.v, w.rs, w.ur, w.level - 1, w.level, *(const uint4*)desc, *(const uint4*)(desc + 16)};
+}
+
+// Candidate test of GetFeaturesInArea + the stereo check on keypoint k at CSR position j; returns the key or kNone.
+__device__ __forceinline__ uint32_t candidate_key(const Probe& p, const FrameView& V, int j, int k) {
+    const spslam_keypoint kp = V.kun[k];
+    const bool check = (p.min_level > 0) || (p.max_level >= 0);
     if (check) {
-        if (kp.octave < w.min_level) return kNone;
-        if (w.max_level >= 0 && kp.octave > w.max_level) return kNone;
+        if (kp.octave < p.min_level) return kNone;
+        if (p.max_level >= 0 && kp.octave > p.max_level) return kNone;
     }
-    const float dx = __fsub_rn(kp.x, w.u), dy = __fsub_rn(kp.y, w.v);
-    if (!(fabsf(dx) < w.r && fabsf(dy) < w.r)) return kNone;
-    const float urk = uright[k];
+    const float dx = __fsub_rn(kp.x, p.u), dy = __fsub_rn(kp.y, p.v);
+    if (!(fabsf(dx) < p.r && fabsf(dy) < p.r)) return kNone;
+    const float urk = V.uright[k];
     if (urk > 0) {
-        const float ur = __fmaf_rn(-g.bf, w.invzc, w.u);
-        const float er = fabsf(__fsub_rn(ur, urk));
-        if (er > w.r) return kNone;
+        const float er = fabsf(__fsub_rn(p.ur, urk));
+        if (er > p.r) return kNone;
     }
-    return ((uint32_t)hamming(d0, d1, desc + 32 * (size_t)k) << 20) | (uint32_t)j;
+    return ((uint32_t)hamming(p.d0, p.d1, V.desc + 32 * (size_t)k) << 20) | (uint32_t)j;
+}
+
+// The K smallest keys over the cells x0 .. x1, y0 .. y1, left in every one of the point's G lanes (sub: this
+// lane's index among them): the cells (column-major, as the reference scans them) are dealt round-robin to the
+// lanes and the lanes' smallest keys merged (unique keys, so the merge is the serial scan's result); x1 < x0 or
+// y1 < y0 (an empty range) gives no cells.  taken: one byte per keypoint, set ones are passed over; may be null.
+template <int K, int G>
+__device__ __forceinline__ void window_keys(const Probe& p, const FrameView& V, int x0, int x1, int y0, int y1,
+                                            const uint8_t* taken, int sub, uint32_t (&bk)[K]) {
+#pragma unroll
+    for (int q = 0; q < K; q++) bk[q] = kNone;
+    const int nrows = y1 - y0 + 1, ncells = x1 >= x0 && nrows > 0 ? (x1 - x0 + 1) * nrows : 0;
+    for (int cell = sub; cell < ncells; cell += G) {
+        const int cx = cell / nrows, c = (x0 + cx) * kRows + y0 + (cell - cx * nrows);
+        const int j0 = V.GO[c], j1 = V.GO[c + 1];
+        for (int j = j0; j < j1; j++) {
+            const int k = V.GI[j];
+            if (taken && taken[k]) continue;
+            insk(bk, candidate_key(p, V, j, k));
+        }
+    }
+#pragma unroll
+    for (int o = G / 2; o >= 1; o >>= 1) {
+        uint32_t pk[K];
+#pragma unroll
+        for (int q = 0; q < K; q++) pk[q] = (uint32_t)__shfl_xor((int)bk[q], o);
+#pragma unroll
+        for (int q = 0; q < K; q++) insk(bk, pk[q]);
+    }
+}
+
+// The window w again by the whole wave, without the keypoints taken by now (LDS bitmap): *m1 / *m2 are the
+// smallest and second smallest key among the candidates this lane tested (every 64th of each cell).
+template <class Win>
+__device__ __forceinline__ void rescan_window(const Probe& p, const FrameView& V, const Win& w, const uint32_t* taken,
+                                              int lane, uint32_t* m1, uint32_t* m2) {
+    uint32_t a = kNone, b = kNone;
+    for (int ix = w.x0; ix <= w.x1; ix++)
+        for (int iy = w.y0; iy <= w.y1; iy++) {
+            const int c = ix * kRows + iy;
+            for (int j = V.GO[c] + lane; j < V.GO[c + 1]; j += 64) {
+                const int k = V.GI[j];
+                if (bit_test(taken, k)) continue;
+                const uint32_t key = candidate_key(p, V, j, k);
+                if (key < a) { b = a; a = key; }
+                else if (key < b) b = key;
+            }
+        }
+    *m1 = a;
+    *m2 = b;
 }
 
 template <int K>
@@ -149,38 +233,12 @@ __global__ __launch_bounds__(kThreads) void match_window_kernel(const spslam_pro
     else if (bwd) { w.min_level = 0; w.max_level = oct; }
     else { w.min_level = oct - 1; w.max_level = oct + 1; }
     w.valid = 1;
-    // GetFeaturesInArea cell range
-    const int x0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, g.min_x), r), g.ginv_x)));
-    const int x1 = min(kCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, g.min_x), r), g.ginv_x)));
-    const int y0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, g.min_y), r), g.ginv_y)));
-    const int y1 = min(kRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, g.min_y), r), g.ginv_y)));
-    if (x0 >= kCols || x1 < 0 || y0 >= kRows || y1 < 0) { if (sub == 0) *W = w; return; }
+    int x0, x1, y0, y1;
+    if (!cell_range(u, v, r, g, &x0, &x1, &y0, &y1)) { if (sub == 0) *W = w; return; }
     w.x0 = (int16_t)x0; w.x1 = (int16_t)x1; w.y0 = (int16_t)y0; w.y1 = (int16_t)y1;
-    const int32_t* GO = C.grid_off + (size_t)f * (kCols * kRows + 1);
-    const int32_t* GI = C.grid_idx + (size_t)f * C.cap;
-    const spslam_keypoint* kun = C.kun + (size_t)f * C.cap;
-    const uint8_t* desc = C.desc + (size_t)f * C.cap * 32;
-    const float* uright = C.uright + (size_t)f * C.cap;
-    const uint4 d0 = *(const uint4*)p.desc, d1 = *(const uint4*)(p.desc + 16);
+    const FrameView V = frame_view(C, f);
     uint32_t bk[K];
-#pragma unroll
-    for (int q = 0; q < K; q++) bk[q] = kNone;
-    // the window's cells (column-major, as the reference scans them) dealt round-robin to the point's lanes;
-    // x1 < x0 or y1 < y0 (an empty range) gives no cells
-    const int nrows = y1 - y0 + 1, ncells = x1 >= x0 && nrows > 0 ? (x1 - x0 + 1) * nrows : 0;
-    for (int cell = sub; cell < ncells; cell += kGrp) {
-        const int cx = cell / nrows, c = (x0 + cx) * kRows + y0 + (cell - cx * nrows);
-        const int j0 = GO[c], j1 = GO[c + 1];
-        for (int j = j0; j < j1; j++) insk(bk, candidate_key(w, C, uright, desc, kun, j, GI[j], d0, d1, g));
-    }
-#pragma unroll
-    for (int o = kGrp / 2; o >= 1; o >>= 1) {
-        uint32_t pk[K];
-#pragma unroll
-        for (int q = 0; q < K; q++) pk[q] = (uint32_t)__shfl_xor((int)bk[q], o);
-#pragma unroll
-        for (int q = 0; q < K; q++) insk(bk, pk[q]);
-    }
+    window_keys<K, kGrp>(probe_of(w, g, p.desc), V, x0, x1, y0, y1, nullptr, sub, bk);
     // lanes 0 .. K-1 resolve best[sub]'s keypoint and angle (read by the in-order walk)
     static_assert(K <= kGrp, "a lane per key");
     uint32_t mine = kNone;
@@ -188,9 +246,9 @@ __global__ __launch_bounds__(kThreads) void match_window_kernel(const spslam_pro
     for (int q = 0; q < K; q++)
         if (sub == q) mine = bk[q];
     if (sub < K && mine != kNone) {
-        const int k = GI[mine & 0xfffff];
+        const int k = V.GI[mine & 0xfffff];
         W->kp[sub] = k;
-        W->kang[sub] = kun[k].angle;
+        W->kang[sub] = V.kun[k].angle;
     }
     if (sub == 0) {
         // kp / kang: written by lanes 0 .. K-1
@@ -201,27 +259,6 @@ __global__ __launch_bounds__(kThreads) void match_window_kernel(const spslam_pro
         for (int q = 0; q < K; q++) W->best[q] = bk[q];
     }
     if (sub < K && mine == kNone) W->kp[sub] = -1;
-}
-
-// ComputeThreeMaxima
-__device__ void three_maxima(const int* h, int* i1, int* i2, int* i3) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < kHisto; i++) {
-        const int s = h[i];
-        if (s > max1) {
-            max3 = max2; max2 = max1; max1 = s;
-            ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (s > max2) {
-            max3 = max2; max2 = s;
-            ind3 = ind2; ind2 = i;
-        } else if (s > max3) {
-            max3 = s;
-            ind3 = i;
-        }
-    }
-    if (max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-    else if (max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-    *i1 = ind1; *i2 = ind2; *i3 = ind3;
 }
 
 template <int K>
@@ -250,14 +287,9 @@ __global__ __launch_bounds__(64) void match_assign_kernel(const spslam_proj_fram
     if (lane < kHisto) hist[lane] = 0;
     __syncthreads();
     const MatchWindowK<K>* Wf = win + (size_t)f * max_points;
-    const int32_t* GO = C.grid_off + (size_t)f * (kCols * kRows + 1);
-    const int32_t* GI = C.grid_idx + (size_t)f * C.cap;
-    const spslam_keypoint* kun = C.kun + (size_t)f * C.cap;
-    const uint8_t* desc = C.desc + (size_t)f * C.cap * 32;
-    const float* uright = C.uright + (size_t)f * C.cap;
+    const FrameView V = frame_view(C, f);
     const spslam_proj_point* P = points + F.point_offset;
     int2* PU = pushes + (size_t)f * max_points;
-    const float factor = __fdiv_rn(1.0f, (float)kHisto);
     int n_push = 0;
 #ifdef SPSLAM_LA_DIAG  // diagnostic build: passes, serial stops and window re-scans per frame (device printf)
     int d_pass = 0, d_stop = 0, d_rescan = 0;
@@ -319,24 +351,19 @@ __global__ __launch_bounds__(64) void match_assign_kernel(const spslam_proj_fram
 #pragma unroll
                 for (int q = 0; q < K; q++) {
                     if (keyl != kNone || rescanl || best[q] == kNone) continue;
-                    if (!((taken[b[q] >> 5] >> (b[q] & 31)) & 1)) { keyl = best[q]; bl = b[q]; kangl = kang[q]; }
+                    if (!bit_test(taken, b[q])) { keyl = best[q]; bl = b[q]; kangl = kang[q]; }
                     else if (q == K - 1) rescanl = true;
                 }
             }
             const bool acc = act && !rescanl && keyl != kNone && (int)(keyl >> 20) <= kThHigh;
             const bool accb = acc && blocking;
             // conflicts with earlier blocking acceptances (the earliest blocking lane per keypoint)
-            auto wsync = [] {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            };
             if (accb) atomicMin(&claim[bl], (uint32_t)lane);
-            wsync();
+            wave_sync();
             const bool conflict = acc && claim[bl] < (uint32_t)lane;
-            wsync();
+            wave_sync();
             if (acc) claim[bl] = 0u;  // reused below as "last committed lane + 1" (0: none)
-            wsync();
+            wave_sync();
             const bool stop = act && (rescanl || (acc && conflict));
             const unsigned long long sm = __ballot(stop);
             const int first = sm ? __ffsll((long long)sm) - 1 : m;
@@ -344,27 +371,22 @@ __global__ __launch_bounds__(64) void match_assign_kernel(const spslam_proj_fram
             const unsigned long long cm = __ballot(commit);
             // the last committed assignment of a keypoint wins, as in the reference's order
             if (commit) atomicMax(&claim[bl], (uint32_t)lane + 1u);
-            wsync();
+            wave_sync();
             const bool last = commit && claim[bl] == (uint32_t)lane + 1u;
-            wsync();
+            wave_sync();
             if (acc) claim[bl] = ~0u;
             int bin = 0;
             if (commit) {
                 if (last) M[bl] = c0 + lane;
-                if (blocking) atomicOr(&taken[bl >> 5], 1u << (bl & 31));
+                if (blocking) bit_set_atomic(taken, bl);
                 if (check_ori) {
-                    float rot = __fsub_rn(pangle, kangl);
-                    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                    bin = (int)roundf(__fmul_rn(rot, factor));
-                    if (bin == kHisto) bin = 0;
+                    bin = rotation_bin(pangle, kangl);
                     atomicAdd(&hist[bin], 1);
                 }
                 PU[n_push + __popcll(cm & ((1ull << lane) - 1ull))] = make_int2(bl, bin);
             }
             n_push += __popcll(cm);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             if (first >= m) break;
 #ifdef SPSLAM_LA_DIAG
             d_stop++;
@@ -381,7 +403,7 @@ __global__ __launch_bounds__(64) void match_assign_kernel(const spslam_proj_fram
                 const int bq = __shfl(b[q], L);
                 const float aq = __shfl(kang[q], L);
                 if (bestL != kNone || rescan || kq == kNone) continue;  // sorted: kNone ends the list
-                if (!((taken[bq >> 5] >> (bq & 31)) & 1)) { bestL = kq; bL = bq; kangL = aq; }
+                if (!bit_test(taken, bq)) { bestL = kq; bL = bq; kangL = aq; }
                 else if (q == K - 1) rescan = true;
             }
             if (rescan) {
@@ -390,24 +412,12 @@ __global__ __launch_bounds__(64) void match_assign_kernel(const spslam_proj_fram
 #endif
                 // an earlier point holds this keypoint: search the window again without the taken ones
                 const MatchWindowK<K> w = Wf[c0 + L];
-                const spslam_proj_point& p = P[c0 + L];
-                const uint4 d0 = *(const uint4*)p.desc, d1 = *(const uint4*)(p.desc + 16);
-                uint32_t mn = kNone;
-                for (int ix = w.x0; ix <= w.x1; ix++)
-                    for (int iy = w.y0; iy <= w.y1; iy++) {
-                        const int c = ix * kRows + iy;
-                        for (int j = GO[c] + lane; j < GO[c + 1]; j += 64) {
-                            const int k = GI[j];
-                            if ((taken[k >> 5] >> (k & 31)) & 1) continue;
-                            mn = min(mn, candidate_key(w, C, uright, desc, kun, j, k, d0, d1, g));
-                        }
-                    }
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, o));
-                bestL = mn;
+                uint32_t m1, m2;
+                rescan_window(probe_of(w, g, P[c0 + L].desc), V, w, taken, lane, &m1, &m2);
+                bestL = wave_min(m1);
                 if (bestL != kNone) {
-                    bL = GI[bestL & 0xfffff];
-                    kangL = kun[bL].angle;
+                    bL = V.GI[bestL & 0xfffff];
+                    kangL = V.kun[bL].angle;
                 }
             }
             start = L + 1;
@@ -416,21 +426,16 @@ __global__ __launch_bounds__(64) void match_assign_kernel(const spslam_proj_fram
             const float pangL = __shfl(pangle, L);
             if (lane == 0) {
                 M[bL] = c0 + L;
-                if (blockL) taken[bL >> 5] |= 1u << (bL & 31);
+                if (blockL) bit_set(taken, bL);
                 int binL = 0;
                 if (check_ori) {
-                    float rot = __fsub_rn(pangL, kangL);
-                    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                    binL = (int)roundf(__fmul_rn(rot, factor));
-                    if (binL == kHisto) binL = 0;
+                    binL = rotation_bin(pangL, kangL);
                     hist[binL]++;
                 }
                 PU[n_push] = make_int2(bL, binL);
             }
             n_push++;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
         }
     }
     __syncthreads();
@@ -447,9 +452,7 @@ __global__ __launch_bounds__(64) void match_assign_kernel(const spslam_proj_fram
                 removed++;
             }
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) removed += __shfl_xor(removed, o);
-        n -= removed;
+        n -= wave_sum(removed);
     }
     if (lane == 0) nmatches[f] = n;
 #ifdef SPSLAM_LA_DIAG
@@ -540,53 +543,21 @@ __global__ __launch_bounds__(kThreads) void local_window_kernel(const spslam_loc
     w.u = u; w.v = v; w.rs = rs; w.ur = __fmaf_rn(-g.bf, invz, u);
     w.level = (int8_t)level;
     w.in_view = 1;
-    const int x0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, g.min_x), rs), g.ginv_x)));
-    const int x1 = min(kCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(u, g.min_x), rs), g.ginv_x)));
-    const int y0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, g.min_y), rs), g.ginv_y)));
-    const int y1 = min(kRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(v, g.min_y), rs), g.ginv_y)));
-    if (x0 >= kCols || x1 < 0 || y0 >= kRows || y1 < 0) { if (sub == 0) *W = w; return; }
+    int x0, x1, y0, y1;
+    if (!cell_range(u, v, rs, g, &x0, &x1, &y0, &y1)) { if (sub == 0) *W = w; return; }
     w.x0 = (int16_t)x0; w.x1 = (int16_t)x1; w.y0 = (int16_t)y0; w.y1 = (int16_t)y1;
-    // the frame-to-frame candidate test with its window: same expressions (ur = fma(-mbf, invz, u))
-    MatchWindow mw{};
-    mw.u = u; mw.v = v; mw.r = rs; mw.invzc = invz;
-    mw.min_level = (int8_t)(level - 1);
-    mw.max_level = (int8_t)level;
-    const int32_t* GO = C.grid_off + (size_t)f * (kCols * kRows + 1);
-    const int32_t* GI = C.grid_idx + (size_t)f * C.cap;
-    const spslam_keypoint* kun = C.kun + (size_t)f * C.cap;
-    const uint8_t* desc = C.desc + (size_t)f * C.cap * 32;
-    const float* uright = C.uright + (size_t)f * C.cap;
-    const uint8_t* tk = taken_in ? taken_in + (size_t)f * C.cap : nullptr;
-    const uint4 d0 = *(const uint4*)p.desc, d1 = *(const uint4*)(p.desc + 16);
+    // the frame-to-frame candidate test with this window, the initially taken keypoints passed over
+    const FrameView V = frame_view(C, f);
     uint32_t bk[K];
-#pragma unroll
-    for (int q = 0; q < K; q++) bk[q] = kNone;
-    // the window's cells dealt round-robin to the point's lanes, the lanes' smallest keys merged (unique keys)
-    const int nrows = y1 - y0 + 1, ncells = x1 >= x0 && nrows > 0 ? (x1 - x0 + 1) * nrows : 0;
-    for (int cell = sub; cell < ncells; cell += kLGrp) {
-        const int cx = cell / nrows, c = (x0 + cx) * kRows + y0 + (cell - cx * nrows);
-        const int j0 = GO[c], j1 = GO[c + 1];
-        for (int j = j0; j < j1; j++) {
-            const int k = GI[j];
-            if (tk && tk[k]) continue;
-            insk(bk, candidate_key(mw, C, uright, desc, kun, j, k, d0, d1, g));
-        }
-    }
-#pragma unroll
-    for (int o = kLGrp / 2; o >= 1; o >>= 1) {
-        uint32_t pk[K];
-#pragma unroll
-        for (int q = 0; q < K; q++) pk[q] = (uint32_t)__shfl_xor((int)bk[q], o);
-#pragma unroll
-        for (int q = 0; q < K; q++) insk(bk, pk[q]);
-    }
+    window_keys<K, kLGrp>(probe_of(w, p.desc), V, x0, x1, y0, y1, taken_in ? taken_in + (size_t)f * C.cap : nullptr,
+                          sub, bk);
     // the keypoint and octave of each key (read by the in-order walk), resolved here
 #pragma unroll
     for (int q = 0; q < K; q++) {
         w.best[q] = bk[q];
         if (bk[q] != kNone) {
-            w.kp[q] = GI[bk[q] & 0xfffff];
-            w.oct[q] = (int8_t)kun[w.kp[q]].octave;
+            w.kp[q] = V.GI[bk[q] & 0xfffff];
+            w.oct[q] = (int8_t)V.kun[w.kp[q]].octave;
         }
     }
     if (sub == 0) *W = w;
@@ -632,11 +603,7 @@ __global__ __launch_bounds__(64) void local_assign_kernel(const spslam_local_fra
     }
     __syncthreads();
     const LocalWindowK<K>* Wf = win + (size_t)f * max_points;
-    const int32_t* GO = C.grid_off + (size_t)f * (kCols * kRows + 1);
-    const int32_t* GI = C.grid_idx + (size_t)f * C.cap;
-    const spslam_keypoint* kun = C.kun + (size_t)f * C.cap;
-    const uint8_t* desc = C.desc + (size_t)f * C.cap * 32;
-    const float* uright = C.uright + (size_t)f * C.cap;
+    const FrameView V = frame_view(C, f);
     const spslam_local_point* Pp = points + F.point_offset;
     int nm = 0;
 #ifdef SPSLAM_LA_DIAG  // diagnostic build: passes, serial stops and window re-scans per frame (device printf)
@@ -693,7 +660,7 @@ __global__ __launch_bounds__(64) void local_assign_kernel(const spslam_local_fra
                 for (int q = 0; q < K; q++) {
                     if (best[q] == kNone) continue;
                     nk++;
-                    if ((taken[b[q] >> 5] >> (b[q] & 31)) & 1) continue;
+                    if (bit_test(taken, b[q])) continue;
                     if (k1 == kNone) { k1 = best[q]; b1 = b[q]; o1 = oc[q]; }
                     else if (k2 == kNone) { k2 = best[q]; b2 = b[q]; o2 = oc[q]; }
                 }
@@ -702,14 +669,10 @@ __global__ __launch_bounds__(64) void local_assign_kernel(const spslam_local_fra
             const bool acc = act && !rescanl && k1 != kNone && ratio_ok(k1, k2, o1, o2);
             // conflict: an earlier accepting lane of this pass takes my best or second-best keypoint
             if (acc) atomicMin(&claim[b1], (uint32_t)lane);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             const bool conflict = act && k1 != kNone &&
                                   (claim[b1] < (uint32_t)lane || (b2 >= 0 && claim[b2] < (uint32_t)lane));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             if (acc) claim[b1] = ~0u;
             const bool stop = act && (rescanl || (k1 != kNone && conflict));
             const unsigned long long sm = __ballot(stop);
@@ -717,12 +680,10 @@ __global__ __launch_bounds__(64) void local_assign_kernel(const spslam_local_fra
             const bool commit = acc && lane < first;
             if (commit) {
                 M[b1] = c0 + lane;
-                atomicOr(&taken[b1 >> 5], 1u << (b1 & 31));
+                bit_set_atomic(taken, b1);
             }
             nm += __popcll(__ballot(commit));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             if (first >= m) break;
             const int L = first;
             start = L + 1;
@@ -736,7 +697,7 @@ __global__ __launch_bounds__(64) void local_assign_kernel(const spslam_local_fra
                 const int bq = __shfl(b[q], L), oq = __shfl(oc[q], L);
                 if (kq == kNone) continue;
                 nk++;
-                if ((taken[bq >> 5] >> (bq & 31)) & 1) continue;
+                if (bit_test(taken, bq)) continue;
                 if (k1 == kNone) { k1 = kq; b1 = bq; o1 = oq; }
                 else if (k2 == kNone) { k2 = kq; o2 = oq; }
             }
@@ -746,53 +707,22 @@ __global__ __launch_bounds__(64) void local_assign_kernel(const spslam_local_fra
                 d_rescan++;
 #endif
                 const LocalWindowK<K> w = Wf[c0 + L];
-                MatchWindow mw{};
-                mw.u = w.u; mw.v = w.v; mw.r = w.rs;
-                mw.invzc = 0.f;
-                mw.min_level = (int8_t)(w.level - 1);
-                mw.max_level = w.level;
-                const spslam_local_point& p = Pp[c0 + L];
-                const uint4 d0 = *(const uint4*)p.desc, d1 = *(const uint4*)(p.desc + 16);
-                uint32_t m1 = kNone, m2 = kNone;
-                for (int ix = w.x0; ix <= w.x1; ix++)
-                    for (int iy = w.y0; iy <= w.y1; iy++) {
-                        const int c = ix * kRows + iy;
-                        for (int j = GO[c] + lane; j < GO[c + 1]; j += 64) {
-                            const int k = GI[j];
-                            if ((taken[k >> 5] >> (k & 31)) & 1) continue;
-                            // candidate_key's stereo test recomputes ur from invzc; use the stored mTrackProjXR
-                            const spslam_keypoint kp = kun[k];
-                            if (kp.octave < mw.min_level || kp.octave > mw.max_level) continue;
-                            if (!(fabsf(__fsub_rn(kp.x, w.u)) < w.rs && fabsf(__fsub_rn(kp.y, w.v)) < w.rs)) continue;
-                            const float urk = uright[k];
-                            if (urk > 0 && fabsf(__fsub_rn(w.ur, urk)) > w.rs) continue;
-                            const uint32_t key = ((uint32_t)hamming(d0, d1, desc + 32 * (size_t)k) << 20) | (uint32_t)j;
-                            if (key < m1) { m2 = m1; m1 = key; }
-                            else if (key < m2) m2 = key;
-                        }
-                    }
+                uint32_t m1, m2;
+                rescan_window(probe_of(w, Pp[c0 + L].desc), V, w, taken, lane, &m1, &m2);
                 // wave top-2: the smallest key, then the smallest key above it
-                uint32_t t1 = m1;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) t1 = min(t1, (uint32_t)__shfl_xor((int)t1, o));
-                uint32_t t2 = m1 == t1 ? m2 : m1;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) t2 = min(t2, (uint32_t)__shfl_xor((int)t2, o));
-                k1 = t1;
-                k2 = t2;
-                b1 = k1 != kNone ? GI[k1 & 0xfffff] : -1;
-                o1 = b1 >= 0 ? kun[b1].octave : -1;
-                o2 = k2 != kNone ? kun[GI[k2 & 0xfffff]].octave : -1;
+                k1 = wave_min(m1);
+                k2 = wave_min(m1 == k1 ? m2 : m1);
+                b1 = k1 != kNone ? V.GI[k1 & 0xfffff] : -1;
+                o1 = b1 >= 0 ? V.kun[b1].octave : -1;
+                o2 = k2 != kNone ? V.kun[V.GI[k2 & 0xfffff]].octave : -1;
             }
             if (k1 == kNone || !ratio_ok(k1, k2, o1, o2)) continue;
             if (lane == 0) {
                 M[b1] = c0 + L;
-                taken[b1 >> 5] |= 1u << (b1 & 31);
+                bit_set(taken, b1);
             }
             nm++;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
         }
     }
     if (lane == 0) nmatches[f] = nm;
@@ -805,6 +735,12 @@ __global__ __launch_bounds__(64) void local_assign_kernel(const spslam_local_fra
 
 }  // namespace match
 
+// Dynamic LDS beyond the default 64 KB needs the per-kernel opt-in: both instantiations (K keys per point) of a walk.
+static hipError_t lds_opt_in(const void* small_batch_kernel, const void* few_keys_kernel, int bytes) {
+    const hipError_t a = hipFuncSetAttribute(small_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return a != hipSuccess ? a : hipFuncSetAttribute(few_keys_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
 hipError_t local_match_launch(int n_frames, const spslam_local_frame* frames, const spslam_local_point* points,
                               int max_points, const MatchCurrent& cur, const MatchGeom& g, const LocalConsts& P,
                               const uint8_t* taken_in, LocalWindow* win, int32_t* match, int* nmatches,
@@ -812,12 +748,8 @@ hipError_t local_match_launch(int n_frames, const spslam_local_frame* frames, co
     // taken bits + the claim table in dynamic LDS (opted in up to 160 KB: caps up to ~39K keypoints)
     const size_t lds = (size_t)((cur.cap + 31) / 32) * 4 + (size_t)cur.cap * 4;
     if (n_frames < 1 || max_points < 0 || cur.cap < 1 || lds > 160 * 1024) return hipErrorInvalidValue;
-    static const hipError_t lds_attr = [] {
-        const hipError_t a = hipFuncSetAttribute((const void*)match::local_assign_kernel<kLocalKeys>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        return a != hipSuccess ? a : hipFuncSetAttribute((const void*)match::local_assign_kernel<kFewKeys>,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }();
+    static const hipError_t lds_attr = lds_opt_in((const void*)match::local_assign_kernel<kLocalKeys>,
+                                                  (const void*)match::local_assign_kernel<kFewKeys>, 160 * 1024);
     if (lds_attr != hipSuccess) return lds_attr;
     if (timer) timer->begin(kKindLocalMatch, s);
     auto run = [&](auto* w) {
@@ -842,12 +774,8 @@ hipError_t match_launch(int n_frames, const spslam_proj_frame* frames, const sps
     // taken bits + the claim table in dynamic LDS (opted in up to 150 KB: caps up to ~36K keypoints)
     const size_t lds = (size_t)((cur.cap + 31) / 32) * 4 + (size_t)cur.cap * 4;
     if (n_frames < 1 || max_points < 0 || cur.cap < 1 || lds > 150 * 1024) return hipErrorInvalidValue;
-    static const hipError_t lds_attr = [] {
-        const hipError_t a = hipFuncSetAttribute((const void*)match::match_assign_kernel<kProjKeys>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        return a != hipSuccess ? a : hipFuncSetAttribute((const void*)match::match_assign_kernel<kFewKeys>,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    }();
+    static const hipError_t lds_attr = lds_opt_in((const void*)match::match_assign_kernel<kProjKeys>,
+                                                  (const void*)match::match_assign_kernel<kFewKeys>, 150 * 1024);
     if (lds_attr != hipSuccess) return lds_attr;
     if (timer) timer->begin(kKindMatch, s);
     const int passes = P.retry_below > 0 ? 2 : 1;

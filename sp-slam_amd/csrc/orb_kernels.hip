@@ -23,6 +23,7 @@
 #include "../../include/spslam_gpu.h"
 #include "wave_priority.h"
 #include "orb_launch.h"
+#include "wave_ops.h"
 
 namespace spslam {
 
@@ -382,18 +383,14 @@ __device__ __forceinline__ void level_tile(const OrbGeom& g, int l, int minTh, i
             ncand += __popcll(m);
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     for (int k = lane; k < ncand; k += 64) {
         const int q = sm.cand[wave][k];
         const int r = q / kLevelTileW, c = q - r * kLevelTileW;
         const int sc = max(fast_score(&sm.tin[r + 3][c + 3], kTinPitch), 0);
         sm.stile[r][c] = (uint8_t)(sc >= minTh ? sc : 0);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     for (int rb = wave * 4; rb < kLevelTileH; rb += kLevelThreads / 16) {
         const int r = rb + lr, y = y0 + r;
         if (active && y < h)
@@ -484,9 +481,7 @@ __global__ __launch_bounds__(256) void fast_cells_kernel(OrbGeom g, uint32_t* __
     const uint8_t* smap = L.score + f * L.blur_frame_stride + (size_t)(iniY + 3) * L.bpitch + (iniX + 3);
     uint32_t* sc32 = reinterpret_cast<uint32_t*>(sc);
     for (int q = lane; q < ((R + 2) * P) >> 2; q += 64) sc32[q] = 0u;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     const float invC = 1.f / (float)max(C, 1);   // p / C exactly for p < 2^12
     for (int p0 = 0; p0 < npx; p0 += 256) {
         uint8_t v[4];
@@ -506,9 +501,7 @@ __global__ __launch_bounds__(256) void fast_cells_kernel(OrbGeom g, uint32_t* __
         for (int k = 0; k < 4; k++)
             if (at[k] >= 0) sc[at[k]] = v[k];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     const int ngroups = R * G;
     const float invG = 1.f / (float)max(G, 1);
     const unsigned long long lt = (1ull << lane) - 1ull;

@@ -25,11 +25,12 @@
 //   N  findLabeledRegionBoundary: Moore tracing from per-pixel 8-neighbour
 //      masks, one wave per plane (count pass, offsets, write pass)
 // Reference semantics are restated in oracle/plane_oracle.cpp:268-470.
-#include "libm_restated.h"
 #include <hip/hip_runtime.h>
 
+#include "pcl_eigen33.h"
 #include "plane_launch.h"
 #include "plane_not_seen.h"
+#include "wave_ops.h"
 
 // The early wave exits below (surplus waves end while the rest of the workgroup still meets __syncthreads)
 // rely on gfx9's s_barrier waiting only for the waves that have not ended.  Other targets keep every wave to
@@ -40,6 +41,8 @@
 
 namespace spslam {
 namespace planes {
+
+using namespace pcl_eigen;
 
 #ifndef SPSLAM_SEG_THREADS
 #define SPSLAM_SEG_THREADS 1024
@@ -151,11 +154,6 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
     const int lane = threadIdx.x & 63;
     return (1ull << lane) - 1ull;
 }
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ void block_sync() {
     __syncthreads();   // workgroup-scope release/acquire (global and LDS)
 }
@@ -176,72 +174,17 @@ __device__ __forceinline__ int wave_excl(int v, int* total) {
     return x - v;
 }
 
-// pcl::computeRoots / eigen33 (float), see oracle/plane_oracle.cpp.
-__device__ void roots2(float b, float c, float* r) {
-    r[0] = 0.f;
-    float d = (float)(b * b - 4.0 * c);
-    if (d < 0.0) d = 0.0;
-    const float sd = sqrtf(d);
-    r[2] = 0.5f * (b + sd);
-    r[1] = 0.5f * (b - sd);
-}
+// pcl::eigen33 (float) for the smallest eigenvalue, see oracle/plane_oracle.cpp.
 __device__ void eigen33_min(const float (&m0)[3][3], float* eval, float* evec) {
-    float scale = 0.f;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) scale = fmaxf(scale, fabsf(m0[i][j]));
-    if (scale <= 1.17549435e-38f) scale = 1.f;
+    const float scale = max_abs3(m0);
     float m[3][3];
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) m[i][j] = m0[i][j] / scale;
     float r[3];
-    const float c0 = m[0][0] * m[1][1] * m[2][2] + 2.f * m[0][1] * m[0][2] * m[1][2] - m[0][0] * m[1][2] * m[1][2] -
-                     m[1][1] * m[0][2] * m[0][2] - m[2][2] * m[0][1] * m[0][1];
-    const float c1 = m[0][0] * m[1][1] - m[0][1] * m[0][1] + m[0][0] * m[2][2] - m[0][2] * m[0][2] +
-                     m[1][1] * m[2][2] - m[1][2] * m[1][2];
-    const float c2 = m[0][0] + m[1][1] + m[2][2];
-    if (fabsf(c0) < 1.1920929e-07f) {
-        roots2(c2, c1, r);
-    } else {
-        const float s_inv3 = (float)(1.0 / 3.0), s_sqrt3 = sqrtf(3.0f);
-        const float c2_over_3 = c2 * s_inv3;
-        float a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
-        if (a_over_3 > 0.f) a_over_3 = 0.f;
-        const float half_b = 0.5f * (c0 + c2_over_3 * (2.f * c2_over_3 * c2_over_3 - c1));
-        float q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
-        if (q > 0.f) q = 0.f;
-        const float rho = sqrtf(-a_over_3);
-        const float theta = libm::atan2f_(sqrtf(-q), half_b) * s_inv3;  // glibc-exact (libm_restated.h)
-        float st, ct;
-        libm::sincosf_(theta, &st, &ct);
-        r[0] = c2_over_3 + 2.f * rho * ct;
-        r[1] = c2_over_3 - rho * (ct + s_sqrt3 * st);
-        r[2] = c2_over_3 - rho * (ct - s_sqrt3 * st);
-        float t;
-        if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
-        if (r[1] >= r[2]) {
-            t = r[1]; r[1] = r[2]; r[2] = t;
-            if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
-        }
-        if (r[0] <= 0) roots2(c2, c1, r);
-    }
+    roots3(m, r);
     *eval = r[0] * scale;
     for (int i = 0; i < 3; i++) m[i][i] -= r[0];
-    float v[3][3];
-    const int pr[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-    float len[3];
-    for (int k = 0; k < 3; k++) {
-        const float* a = m[pr[k][0]];
-        const float* b = m[pr[k][1]];
-        v[k][0] = a[1] * b[2] - a[2] * b[1];
-        v[k][1] = a[2] * b[0] - a[0] * b[2];
-        v[k][2] = a[0] * b[1] - a[1] * b[0];
-        len[k] = v[k][0] * v[k][0] + v[k][1] * v[k][1] + v[k][2] * v[k][2];
-    }
-    int k = 2;
-    if (len[0] >= len[1] && len[0] >= len[2]) k = 0;
-    else if (len[1] >= len[0] && len[1] >= len[2]) k = 1;
-    const float sl = sqrtf(len[k]);
-    for (int j = 0; j < 3; j++) evec[j] = v[k][j] / sl;
+    eigenvector_of(m, evec);
 }
 
 // Eigen SSE predux order for a Vector4f dot.

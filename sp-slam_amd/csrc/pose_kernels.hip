@@ -33,6 +33,7 @@
 #include "../../include/spslam_gpu.h"
 #include "g2o_device.h"
 #include "pose_launch.h"
+#include "wave_ops.h"
 
 // Phase profile (diagnostic build only: make prof -> libspslam_gpu_prof.so).  Thread 0 of every problem
 // accumulates wall_clock64 ticks (100 MHz) per phase; spslam_pose_prof_read returns the grid totals.
@@ -342,11 +343,6 @@ __device__ __forceinline__ int lds_acquire(const int* p) {
 __device__ __forceinline__ void lds_publish(int* p, int v) {  // after this wave's ring writes (every lane fences)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     if ((threadIdx.x & 63) == 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // rows below this are staged (every compute wave's share of every earlier round, and the leading waves' shares

@@ -28,14 +28,15 @@
 // fitted lines in order: CaculatePlanes + PlaneNotSeen against the growing
 // plane list (serial, as in the reference), then the synthetic patches and
 // line point lists are written by all lanes.
-#include <cfloat>
-
-#include "libm_restated.h"
+#include "pcl_eigen33.h"
 #include "plane_not_seen.h"
 #include "supposed_launch.h"
+#include "wave_ops.h"
 
 namespace spslam {
 namespace supp {
+
+using namespace pcl_eigen;
 
 constexpr int kThreads = 256, kWaves = 4;  // the batched launch (one workgroup per boundary)
 constexpr int kMaxWaves = 8;                // small batches: 512 threads (supp_launch)
@@ -62,11 +63,6 @@ struct Shared {
     int s0x[kBatch], s1x[kBatch], nbb[2], failb[2];  // kOverlap: the second sample buffer, both buffers' counts
 };
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 template <int NT>
 __device__ int block_sum(int v, Shared& S) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -108,51 +104,6 @@ __device__ __forceinline__ float line_sqd(const float* lp, const float* ld, cons
     return (cx * cx + cz * cz) + (cy * cy + 0.f);
 }
 
-// pcl::computeRoots on a scaled matrix (float), glibc-exact transcendental calls.
-__device__ void roots2(float b, float c, float* r) {
-    r[0] = 0.f;
-    float d = (float)(b * b - 4.0 * c);
-    if (d < 0.0) d = 0.0;
-    const float sd = sqrtf(d);
-    r[2] = 0.5f * (b + sd);
-    r[1] = 0.5f * (b - sd);
-}
-__device__ void roots3(const float (&m)[3][3], float* r) {
-    const float c0 = m[0][0] * m[1][1] * m[2][2] + 2.f * m[0][1] * m[0][2] * m[1][2] - m[0][0] * m[1][2] * m[1][2] -
-                     m[1][1] * m[0][2] * m[0][2] - m[2][2] * m[0][1] * m[0][1];
-    const float c1 = m[0][0] * m[1][1] - m[0][1] * m[0][1] + m[0][0] * m[2][2] - m[0][2] * m[0][2] +
-                     m[1][1] * m[2][2] - m[1][2] * m[1][2];
-    const float c2 = m[0][0] + m[1][1] + m[2][2];
-    if (fabsf(c0) < FLT_EPSILON) { roots2(c2, c1, r); return; }
-    const float s_inv3 = (float)(1.0 / 3.0), s_sqrt3 = sqrtf(3.0f);
-    const float c2_over_3 = c2 * s_inv3;
-    float a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
-    if (a_over_3 > 0.f) a_over_3 = 0.f;
-    const float half_b = 0.5f * (c0 + c2_over_3 * (2.f * c2_over_3 * c2_over_3 - c1));
-    float q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
-    if (q > 0.f) q = 0.f;
-    const float rho = sqrtf(-a_over_3);
-    const float theta = libm::atan2f_(sqrtf(-q), half_b) * s_inv3;
-    float st, ct;
-    libm::sincosf_(theta, &st, &ct);
-    r[0] = c2_over_3 + 2.f * rho * ct;
-    r[1] = c2_over_3 - rho * (ct + s_sqrt3 * st);
-    r[2] = c2_over_3 - rho * (ct - s_sqrt3 * st);
-    float t;
-    if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
-    if (r[1] >= r[2]) {
-        t = r[1]; r[1] = r[2]; r[2] = t;
-        if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
-    }
-    if (r[0] <= 0) roots2(c2, c1, r);
-}
-__device__ float max_abs3(const float (&m)[3][3]) {
-    float s = 0.f;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) s = fmaxf(s, fabsf(m[i][j]));
-    if (s <= FLT_MIN) s = 1.f;
-    return s;
-}
 // pcl::eigen33(cov, evals) + computeCorrespondingEigenVector(cov, evals[2]).
 __device__ void line_direction(const float (&cov)[3][3], float* evec) {
     const float scale = max_abs3(cov);
@@ -167,21 +118,7 @@ __device__ void line_direction(const float (&cov)[3][3], float* evec) {
         for (int j = 0; j < 3; j++) s[i][j] = cov[i][j] / scale2;
     const float sub = eval2 / scale2;
     for (int i = 0; i < 3; i++) s[i][i] -= sub;
-    const int pr[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-    float v[3][3], len[3];
-    for (int k = 0; k < 3; k++) {
-        const float* a = s[pr[k][0]];
-        const float* b = s[pr[k][1]];
-        v[k][0] = a[1] * b[2] - a[2] * b[1];
-        v[k][1] = a[2] * b[0] - a[0] * b[2];
-        v[k][2] = a[0] * b[1] - a[1] * b[0];
-        len[k] = v[k][0] * v[k][0] + v[k][1] * v[k][1] + v[k][2] * v[k][2];
-    }
-    int k = 2;
-    if (len[0] >= len[1] && len[0] >= len[2]) k = 0;
-    else if (len[1] >= len[0] && len[1] >= len[2]) k = 1;
-    const float sl = sqrtf(len[k]);
-    for (int j = 0; j < 3; j++) evec[j] = v[k][j] / sl;
+    eigenvector_of(s, evec);
 }
 
 struct Cam { float fx, fy, cx, cy, min_x, max_x, min_y, max_y; int w, h, stride; };

@@ -16,6 +16,7 @@
 #include "wave_priority.h"
 
 #include "track_launch.h"
+#include "wave_ops.h"
 
 namespace spslam {
 
@@ -362,8 +363,7 @@ __global__ __launch_bounds__(kThreads) void refkf_kernel(spslam_track_batch B, s
     const spslam_pose_problem& P = B.problems[f];
     for (int j = t; j < P.n_planes; j += kThreads)
         if (B.planes[P.plane_offset + j].kind == SPSLAM_PLANE_EDGE && !B.plane_outlier[P.plane_offset + j]) c++;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
+    c = wave_sum(c);
     if (lane == 0) wsum[wave] = c;
     __syncthreads();
     if (t != 0) return;
