@@ -382,25 +382,54 @@ typedef struct spslam_plane {
     int32_t contour_offset;   /* into the frame's contour index buffer */
 } spslam_plane;
 
-/* Configure (and allocate scratch for max_batch frames) the plane stage. */
+/* Configure (and allocate scratch for max_batch frames) the plane stage.
+ * SPSLAM_ERR_ARG for a geometry no kernel instance takes, so that an extraction never refuses a configured
+ * one.  The organized cloud is W = ceil(width / cloud_dis) columns by H = ceil(height / cloud_dis) rows:
+ *   W <= 512 (eight 64-bit row words) and H <= 512 (one lane per row in the distance-map kernels),
+ *   N = W * H <= 160000.
+ * There is no lower bound: clouds down to 1 x 1 are extracted (a cloud of 20 or fewer rows or columns has
+ * no valid normal, IntegralImageNormalEstimation's border being 10, and so no plane). */
 int spslam_planes_configure(spslam_ctx* ctx, const spslam_plane_params* params);
 
 /* Capacities the caller must provide per frame: planes, inlier indices,
- * contour indices. */
+ * contour indices.
+ *
+ * Limits the reference does not have (the segmentation kernel's LDS tables rest on them).  Per frame at most
+ *   255 connected components larger than Plane.MinSize (in label order; later ones are not fitted),
+ *   64 plane models (components passing the curvature test, in label order; later ones are dropped), and
+ *   64 kept planes (planes_cap).
+ * A frame past a limit still yields well-formed output (counts[f] <= planes_cap, every offset + length
+ * within the capacities), but not the reference's planes.  It is reported: see spslam_planes_status. */
 int spslam_planes_capacity(const spslam_ctx* ctx, int* planes_cap, int* inlier_cap, int* contour_cap);
 
+/* Limits a frame crossed (spslam_planes_status flags). */
+#define SPSLAM_PLANES_OVER_COMPONENTS 1 /* more than 255 components larger than Plane.MinSize */
+#define SPSLAM_PLANES_OVER_MODELS 2     /* more than 64 plane models */
+#define SPSLAM_PLANES_OVER_KEPT 4       /* more kept planes than planes_cap: reserved.  Every entry passes
+                                           planes_cap = 64, the model limit, so today it is never set. */
+
 /* Drop-in for one frame, host buffers.  *n_planes receives the plane count;
- * inliers / contours receive the index lists referenced by planes[]. */
+ * inliers / contours receive the index lists referenced by planes[].
+ * SPSLAM_ERR_CAPACITY (outputs filled as far as the limits go, the message names the limit) when the frame
+ * crossed one of the limits above. */
 int spslam_planes_extract(spslam_ctx* ctx, const float* depth, int w, int h, int stride_floats,
                           spslam_plane* planes, int planes_cap, int* n_planes, int32_t* inliers, int32_t* contours);
 
 /* Batched, device resident: frame f's depth at d_depth + f*frame_stride
  * floats (rows stride_floats apart).  Per frame f: counts[f] planes at
  * d_planes + f*planes_cap, indices at d_inliers + f*inlier_cap and
- * d_contours + f*contour_cap (capacities from spslam_planes_capacity). */
+ * d_contours + f*contour_cap (capacities from spslam_planes_capacity).
+ * Asynchronous: a frame past a limit does not change the return value; ask spslam_planes_status. */
 int spslam_planes_extract_batch_device(spslam_ctx* ctx, const float* d_depth, int n_frames, size_t frame_stride,
                                        int stride_floats, spslam_plane* d_planes, int* d_counts,
                                        int32_t* d_inliers, int32_t* d_contours, void* hip_stream);
+
+/* *flags = the SPSLAM_PLANES_OVER_* limits frame `frame` of the last extraction crossed (0: none).  Call it
+ * after synchronising the stream the extraction ran on; it copies eight bytes from the device.
+ * Only the most recently enqueued extraction can be asked: once the next one is enqueued (as a pipelined
+ * caller does before the first has finished), the flags of the earlier call read as 0 and are lost.  A caller
+ * that needs them asks between the two calls. */
+int spslam_planes_status(spslam_ctx* ctx, int frame, int* flags);
 
 /* ------------------------------------------------------------------------
  * Supposed planes: Frame::GeneratePlanesFromBoundries (include/Frame.h:121,
@@ -491,6 +520,18 @@ int spslam_planes_debug(spslam_ctx* ctx, int frame, int what, void* out, int* n_
  * spslam_planes_debug(what = 3) returns.  Off by default: frames whose union-find runs in LDS (16-bit labels)
  * then write no label map at all. */
 int spslam_debug_plane_labels(spslam_ctx* ctx, int keep);
+
+/* Test hook: the kernels an extraction of n_frames frames launches under the current configuration, from
+ * the functions the launch itself dispatches on (nothing runs). */
+typedef struct spslam_plane_launch_shape {
+    int32_t seg_maps_in_lds;  /* segmentation: per-frame maps and 16-bit union-find parents in LDS (1) or global (0) */
+    int32_t seg_positions;    /* segmentation: row positions per lane of the refinement scans, 4 or 8 */
+    int32_t wave_count;       /* distance map / integral images: waves per workgroup, ceil(H / 64) */
+    int32_t one_workgroup;    /* 1: one workgroup per frame (plane_wave_kernel), 0: three (plane_wave_roles_kernel) */
+    int32_t barrier_rows;     /* 0, or the row bound (192, 320, 512) of the barrier kernel
+                                 SPSLAM_PLANE_WAVE_BARRIER=1 selects instead of either */
+} spslam_plane_launch_shape;
+int spslam_debug_plane_launch_shape(spslam_ctx* ctx, int n_frames, spslam_plane_launch_shape* shape);
 
 /* Test hook: Frame::PlaneNotSeen (src/Frame.cc:1116-1130) of each of n_coefs
  * candidate coefficient vectors against n_planes planes (4 floats each, host

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include <random>
+#include <string>
 
 namespace {
 
@@ -66,6 +67,9 @@ hipError_t configure_supposed(spslam_ctx* c, const spslam_plane_params* p) {
     return c->d_patch1.alloc(sp.supp_cap * patch * 12);
 }
 
+// The limits a frame's status word (PlaneBuffers::ts[14]) names, if it is of extraction call `epoch`.
+int plane_status_flags(long long word, int epoch) { return (word >> 8) == epoch ? (int)(word & 0xFF) : 0; }
+
 }  // namespace
 
 extern "C" {
@@ -76,7 +80,7 @@ int spslam_planes_configure(spslam_ctx* c, const spslam_plane_params* p) {
         return fail(c, SPSLAM_ERR_ARG, "bad plane parameters%s", "");
     HIP_CHECK(c, hipSetDevice(c->device));
     HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    PlaneGeom& g = c->pg;
+    PlaneGeom g = c->pg;  // (a refused geometry leaves the context's configuration as it was)
     g.w = p->width;
     g.h = p->height;
     g.ds = p->cloud_dis;
@@ -86,12 +90,17 @@ int spslam_planes_configure(spslam_ctx* c, const spslam_plane_params* p) {
     if (g.H > 512) return fail(c, SPSLAM_ERR_ARG, "organized cloud taller than 512 rows%s", "");
     if (g.N > 160000) return fail(c, SPSLAM_ERR_ARG, "organized cloud larger than the LDS state map%s", "");
     if (3 * 10 * g.W * 4 > 65536) return fail(c, SPSLAM_ERR_ARG, "organized cloud wider than the LDS row band%s", "");
+    // whatever plane_launch would refuse at extraction time is refused here
+    if (plane_launch_shape(g, 1, nullptr) != hipSuccess)
+        return fail(c, SPSLAM_ERR_ARG, "no kernel instance takes the organized cloud%s",
+                    g.W > 512 ? ": wider than 512 columns" : ": past the segmentation's LDS or index budget");
     g.fx = p->fx; g.fy = p->fy; g.cx = p->cx; g.cy = p->cy;
     g.min_size = p->min_size;
     g.ang_cos = std::cos((float)(0.017453 * p->angle_threshold));  // cosf(static_cast<float>(0.017453*AngTh))
     g.dist_th = p->distance_threshold;
     g.inlier_cap = g.N;
     g.contour_cap = 4 * g.N;
+    c->pg = g;
     const long long N = g.N, F = c->p.max_batch, IWH = (long long)(g.W + 1) * (g.H + 1);
     PlaneBuffers& b = c->pb;
     // nothing of the old configuration stays reachable until every buffer of the new one exists
@@ -126,6 +135,7 @@ int spslam_planes_configure(spslam_ctx* c, const spslam_plane_params* p) {
     b.grown = (int*)carve(F * b.grown_fs * 4);
     b.maps = (uint8_t*)carve(F * b.maps_fs);
     b.ts = (long long*)carve(F * 16 * sizeof(long long));
+    HIP_CHECK(c, hipMemset(b.ts, 0, F * 16 * sizeof(long long)));  // no frame has crossed a limit (ts[14])
     HIP_CHECK(c, c->d_depth_in.alloc((size_t)g.w * g.h * sizeof(float)));
     HIP_CHECK(c, c->d_planes1.alloc(kMaxPlanesPerFrame * sizeof(spslam_plane)));
     HIP_CHECK(c, c->d_plane_cnt1.alloc(16));
@@ -159,6 +169,7 @@ int spslam_planes_extract_batch_device(spslam_ctx* c, const float* d_depth, int 
     const bool have_cloud = tag.depth == d_depth && n_frames <= tag.n &&
                             frame_stride == (size_t)c->pg.w * c->pg.h && stride_floats == c->pg.w;
     tag = {};
+    c->pb.epoch++;
     HIP_CHECK(c, plane_launch(c->pg, c->pb, n_frames, d_depth, (long long)frame_stride, stride_floats, d_planes,
                               d_counts, kMaxPlanesPerFrame, d_inliers, d_contours, s, c->timer, have_cloud));
     c->plane_last_frames = n_frames;
@@ -178,12 +189,15 @@ int spslam_planes_extract(spslam_ctx* c, const float* depth, int w, int h, int s
                                                 c->d_inl1, c->d_con1, c->stream);
     if (rc) return rc;
     int n = 0;
+    long long word = 0;
     spslam_plane tmp[kMaxPlanesPerFrame];
     HIP_CHECK(c, hipMemcpyAsync(&n, c->d_plane_cnt1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(&word, c->pb.ts + 14, sizeof word, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(c, hipMemcpyAsync(tmp, c->d_planes1, sizeof tmp, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(c, hipStreamSynchronize(c->stream));
     *n_planes = n;
     if (n > planes_cap) return fail(c, SPSLAM_ERR_CAPACITY, "plane buffer too small%s", "");
+    const int over = plane_status_flags(word, c->pb.epoch);
     int ni = 0, nc = 0;
     for (int k = 0; k < n; k++) {
         planes[k] = tmp[k];
@@ -192,6 +206,32 @@ int spslam_planes_extract(spslam_ctx* c, const float* depth, int w, int h, int s
     }
     if (inliers && ni) HIP_CHECK(c, hipMemcpy(inliers, c->d_inl1, (size_t)ni * 4, hipMemcpyDeviceToHost));
     if (contours && nc) HIP_CHECK(c, hipMemcpy(contours, c->d_con1, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    if (over) {
+        std::string what;
+        if (over & SPSLAM_PLANES_OVER_COMPONENTS) what += " more than 255 components over Plane.MinSize;";
+        if (over & SPSLAM_PLANES_OVER_MODELS) what += " more than 64 plane models;";
+        if (over & SPSLAM_PLANES_OVER_KEPT) what += " more than 64 kept planes;";
+        return fail(c, SPSLAM_ERR_CAPACITY, "plane extraction limit crossed:%s", what.c_str());
+    }
+    return SPSLAM_OK;
+}
+
+int spslam_planes_status(spslam_ctx* c, int frame, int* flags) {
+    if (!c || !flags) return SPSLAM_ERR_ARG;
+    if (!c->planes_ready || frame < 0 || frame >= c->plane_last_frames)
+        return fail(c, SPSLAM_ERR_NOT_READY, "no plane data for that frame%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    long long word = 0;
+    HIP_CHECK(c, hipMemcpy(&word, c->pb.ts + (size_t)frame * 16 + 14, sizeof word, hipMemcpyDeviceToHost));
+    *flags = plane_status_flags(word, c->pb.epoch);
+    return SPSLAM_OK;
+}
+
+int spslam_debug_plane_launch_shape(spslam_ctx* c, int n_frames, spslam_plane_launch_shape* shape) {
+    if (!c || !shape || n_frames < 1) return SPSLAM_ERR_ARG;
+    if (!c->planes_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_planes_configure not called%s", "");
+    if (plane_launch_shape(c->pg, n_frames, shape) != hipSuccess)
+        return fail(c, SPSLAM_ERR_ARG, "no kernel instance takes the configured cloud%s", "");
     return SPSLAM_OK;
 }
 

@@ -48,6 +48,14 @@ __device__ __forceinline__ bool dc_bad(float za, float zb) {
     return fabsf(za - zb) > thr || !isfinite(za) || !isfinite(zb);
 }
 
+// IntegralImage2D::computeIntegralImages leaves out an element whose sum is not finite (a gradient with a NaN or
+// infinite neighbour).  As zeros here: the running sums are never -0, so adding +0 leaves them bit for bit.  (Its
+// finite-element count is not kept: a point with smoothing > 2 has no depth change, so no such element, within its
+// window, and the count test of computePointNormal never fires.)
+__device__ __forceinline__ void skip_nonfinite(float& a, float& b, float& c) {
+    if (!isfinite(a + b + c)) a = b = c = 0.f;
+}
+
 // Initial distance-map value of cell (r, c): 0 where the depth-change map is 0.  z(r, c) reads the
 // cloud's z.
 template <class ZAt>
@@ -160,6 +168,8 @@ __global__ __launch_bounds__(MAXR) void plane_dist_integral_kernel(PlaneGeom g, 
                 o.e[k] = at(k, r, c + 1) - at(k, r, c - 1);
                 o.e[3 + k] = at(k, r + 1, c) - at(k, r - 1, c);
             }
+            skip_nonfinite(o.e[0], o.e[1], o.e[2]);
+            skip_nonfinite(o.e[3], o.e[4], o.e[5]);
         }
         return o;
     };
@@ -424,6 +434,8 @@ __global__ __launch_bounds__(64 * NWV) void plane_wave_kernel(PlaneGeom g, const
             if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
                 e[0] = wx[j + 3] - wx[j + 1]; e[1] = wy[j + 3] - wy[j + 1]; e[2] = wz[j + 3] - wz[j + 1];
                 e[3] = dx - ux; e[4] = dy - uy; e[5] = dz - uz;
+                skip_nonfinite(e[0], e[1], e[2]);
+                skip_nonfinite(e[3], e[4], e[5]);
             }
             // PCL's pass 1 and IntegralImage2D's recurrence (plane_dist_integral_kernel step1)
             const bool ok = row_ok && c >= 0 && c < W, inner = r > 0 && c > 0;
@@ -673,6 +685,7 @@ __device__ __forceinline__ void plane_wave_role(const PlaneGeom& g, const float*
                 if constexpr (ROLE == 1) {
                     if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
                         e[0] = wx[j + 3] - wx[j + 1]; e[1] = wy[j + 3] - wy[j + 1]; e[2] = wz[j + 3] - wz[j + 1];
+                        skip_nonfinite(e[0], e[1], e[2]);
                     }
                 } else {
                     float ux = from_above(wx[j]), uy = from_above(wy[j]), uz = from_above(wz[j]);
@@ -681,6 +694,7 @@ __device__ __forceinline__ void plane_wave_role(const PlaneGeom& g, const float*
                     if (lane == 63 && has_dn) { dx = DN[cc]; dy = DN[W + cc]; dz = DN[2 * W + cc]; }
                     if (r >= 1 && r <= H - 2 && c >= 1 && c <= W - 2) {
                         e[0] = dx - ux; e[1] = dy - uy; e[2] = dz - uz;
+                        skip_nonfinite(e[0], e[1], e[2]);
                     }
                 }
                 double iv[3];
@@ -847,20 +861,13 @@ __global__ __launch_bounds__(256) void plane_normal_kernel(PlaneGeom g, const fl
 
 using namespace planes;
 
-hipError_t plane_launch(const PlaneGeom& g, const PlaneBuffers& b, int n, const float* depth, long long depth_fs,
-                        int depth_stride, spslam_plane* planes, int* plane_counts, int planes_cap, int32_t* inliers,
-                        int32_t* contours, hipStream_t s, KernelTimer* timer, bool have_cloud) {
-    if (g.H > kWaveThreads) return hipErrorInvalidValue;
-    auto B = [&](int k) { if (timer) timer->begin(k, s); };
-    auto E = [&](int k) { if (timer) timer->end(k, s); };
-    const dim3 pts((g.N + 255) / 256, n);
-    if (!have_cloud) {  // (else a fused grab made it: grab_kernels.hip)
-        B(kKindPlaneCloud);
-        hipLaunchKernelGGL(plane_cloud_kernel, pts, dim3(256), 0, s, g, depth, depth_fs, depth_stride, b.cloud,
-                           b.cloud_fs);
-        E(kKindPlaneCloud);
-    }
-    B(kKindPlaneDist);
+// Which kernels a call over n frames launches.  plane_launch dispatches on this and nothing else, and
+// spslam_planes_configure refuses what it refuses.
+hipError_t plane_launch_shape(const PlaneGeom& g, int n, spslam_plane_launch_shape* out) {
+    spslam_plane_launch_shape sh{};
+    if (g.W < 1 || g.H < 1 || g.H > kWaveThreads) return hipErrorInvalidValue;
+    const hipError_t se = plane_segment_shape(g, &sh.seg_maps_in_lds, &sh.seg_positions);
+    if (se != hipSuccess) return se;
     static const bool barrier_wave = [] {
         const char* e = getenv("SPSLAM_PLANE_WAVE_BARRIER");
         return e && e[0] == '1';
@@ -873,19 +880,38 @@ hipError_t plane_launch(const PlaneGeom& g, const PlaneBuffers& b, int n, const 
         const char* e = getenv("SPSLAM_PLANE_WAVE");
         return e ? atoi(e) : 0;
     }();
-    const bool one_wave_group = wave_groups == 1 || (wave_groups != 3 && n > 16);
-    if (!barrier_wave && !one_wave_group) {
-        const int nw = (g.H + 63) / 64;
-        const size_t lds = (size_t)nw * 6 * g.W * sizeof(float);
+    sh.wave_count = (g.H + 63) / 64;
+    sh.one_workgroup = wave_groups == 1 || (wave_groups != 3 && n > 16);
+    sh.barrier_rows = !barrier_wave ? 0 : g.H <= 192 ? 192 : g.H <= 320 ? 320 : kWaveThreads;
+    if (out) *out = sh;
+    return hipSuccess;
+}
+
+hipError_t plane_launch(const PlaneGeom& g, const PlaneBuffers& b, int n, const float* depth, long long depth_fs,
+                        int depth_stride, spslam_plane* planes, int* plane_counts, int planes_cap, int32_t* inliers,
+                        int32_t* contours, hipStream_t s, KernelTimer* timer, bool have_cloud) {
+    spslam_plane_launch_shape sh;
+    if (const hipError_t e = plane_launch_shape(g, n, &sh); e != hipSuccess) return e;
+    auto B = [&](int k) { if (timer) timer->begin(k, s); };
+    auto E = [&](int k) { if (timer) timer->end(k, s); };
+    const dim3 pts((g.N + 255) / 256, n);
+    if (!have_cloud) {  // (else a fused grab made it: grab_kernels.hip)
+        B(kKindPlaneCloud);
+        hipLaunchKernelGGL(plane_cloud_kernel, pts, dim3(256), 0, s, g, depth, depth_fs, depth_stride, b.cloud,
+                           b.cloud_fs);
+        E(kKindPlaneCloud);
+    }
+    B(kKindPlaneDist);
+    const int nw = sh.wave_count;
+    const size_t lds = (size_t)nw * 6 * g.W * sizeof(float);
+    if (!sh.barrier_rows && !sh.one_workgroup) {
         auto* k = nw <= 1 ? plane_wave_roles_kernel<1> : nw <= 2 ? plane_wave_roles_kernel<2>
                 : nw <= 3 ? plane_wave_roles_kernel<3> : nw <= 4 ? plane_wave_roles_kernel<4>
                 : nw <= 5 ? plane_wave_roles_kernel<5> : nw <= 6 ? plane_wave_roles_kernel<6>
                 : nw <= 7 ? plane_wave_roles_kernel<7> : plane_wave_roles_kernel<8>;
         hipLaunchKernelGGL(k, dim3(n, 3), dim3(64 * nw), lds, s, g, depth, depth_fs, depth_stride, b.wave, b.wave_fs,
                            b.dist, b.dist_fs, b.integral, b.integral_fs);
-    } else if (!barrier_wave) {
-        const int nw = (g.H + 63) / 64;
-        const size_t lds = (size_t)nw * 6 * g.W * sizeof(float);
+    } else if (!sh.barrier_rows) {
         auto* k = nw <= 1 ? plane_wave_kernel<1> : nw <= 2 ? plane_wave_kernel<2> : nw <= 3 ? plane_wave_kernel<3>
                 : nw <= 4 ? plane_wave_kernel<4> : nw <= 5 ? plane_wave_kernel<5> : nw <= 6 ? plane_wave_kernel<6>
                 : nw <= 7 ? plane_wave_kernel<7> : plane_wave_kernel<8>;
@@ -893,9 +919,9 @@ hipError_t plane_launch(const PlaneGeom& g, const PlaneBuffers& b, int n, const 
                            b.dist, b.dist_fs, b.integral, b.integral_fs);
     } else {
         const int rows = wave_pitch(g.H);
-        auto* k = g.H <= 192   ? plane_dist_integral_kernel<192, kWaveChunk>
-                  : g.H <= 320 ? plane_dist_integral_kernel<320, kWaveChunk>
-                               : plane_dist_integral_kernel<kWaveThreads, kWaveChunk / 2>;  // (LDS: 155 KB)
+        auto* k = sh.barrier_rows == 192   ? plane_dist_integral_kernel<192, kWaveChunk>
+                  : sh.barrier_rows == 320 ? plane_dist_integral_kernel<320, kWaveChunk>
+                                           : plane_dist_integral_kernel<kWaveThreads, kWaveChunk / 2>;  // (LDS: 155 KB)
         hipLaunchKernelGGL(k, dim3(n), dim3(rows), 0, s, g, depth, depth_fs, depth_stride, b.wave, b.wave_fs, b.dist,
                            b.dist_fs, b.integral, b.integral_fs);
     }

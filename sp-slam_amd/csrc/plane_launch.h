@@ -38,6 +38,9 @@ struct PlaneBuffers {
     long long* ts;       // [F][16] segmentation phase stamps (s_memrealtime, 100 MHz), diagnostics
     long long cloud_fs, wave_fs, dist_fs, integral_fs, normal_fs, pd_fs, labels_fs, work_fs, grown_fs, maps_fs;
     int keep_labels;     // the LDS instance also stores the connected-component labels in `labels` (test hook)
+    // Number of the extraction call, from 1.  A frame past a limit stores (epoch << 8 | SPSLAM_PLANES_OVER_*) in its
+    // ts[14]; a frame within the limits stores nothing, and spslam_planes_status tells a stale word by its epoch.
+    int epoch;
 };
 
 // Skewed wavefront layout: entry (st, r) = cloud cell (r, c = st - 2r), the cell wavefront step st
@@ -56,6 +59,12 @@ __host__ __device__ inline long long wave_size(int W, int H) {
 __host__ __device__ inline long long wave_index(int r, int c, int H) {
     return (long long)(c + 2 * r + kWaveChunk) * wave_pitch(H) + r;
 }
+
+// The kernels plane_launch picks for n frames of this geometry (environment switches included); hipErrorInvalidValue
+// for a geometry it refuses.  plane_launch dispatches on the result; spslam_planes_configure refuses what it refuses.
+hipError_t plane_launch_shape(const PlaneGeom& g, int n, spslam_plane_launch_shape* out);
+// The segmentation part of it (plane_segment.hip).
+hipError_t plane_segment_shape(const PlaneGeom& g, int* in_lds, int* k);
 
 hipError_t plane_launch(const PlaneGeom& g, const PlaneBuffers& b, int n, const float* depth, long long depth_fs,
                         int depth_stride, spslam_plane* planes, int* plane_counts, int planes_cap,

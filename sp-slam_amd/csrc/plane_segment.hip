@@ -909,6 +909,7 @@ __global__ __launch_bounds__(kSegThreads) void plane_segment_kernel(
         __syncthreads();
         if (t == 0) {
             S.nbig = min(nbig, kMaxBig);
+            S.misc[7] = nbig > kMaxBig ? SPSLAM_PLANES_OVER_COMPONENTS : 0;  // limits crossed (thread 0's alone)
             int off = 0;
             for (int j = 0; j < S.nbig; j++) { S.big_off[j] = off; off += S.big_size[j]; }
         }
@@ -1106,6 +1107,7 @@ __global__ __launch_bounds__(kSegThreads) void plane_segment_kernel(
                 pp[3] = -1 * dot4(pp, S.big_cen[j]);
             }
             S.big_state[j + 1] = 0;
+            if (S.big_curv[j] < 0.001f && nm >= kMaxPlanesPerFrame) S.misc[7] |= SPSLAM_PLANES_OVER_MODELS;
             if (S.big_curv[j] < 0.001f && nm < kMaxPlanesPerFrame) {
                 S.model_big[nm] = j;
                 for (int k = 0; k < 4; k++) S.model_coef[nm][k] = pp[k];
@@ -1224,6 +1226,7 @@ __global__ __launch_bounds__(kSegThreads) void plane_segment_kernel(
             for (int q = 0; q < nk && !seen; q++) {
                 seen = plane_seen_by(planes[q].coef, cf);
             }
+            if (!seen && nk >= planes_cap) S.misc[7] |= SPSLAM_PLANES_OVER_KEPT;
             if (seen || nk >= planes_cap) continue;
             for (int k = 0; k < 4; k++) planes[nk].coef[k] = cf[k];
             S.kept[nk++] = m;
@@ -1238,6 +1241,8 @@ __global__ __launch_bounds__(kSegThreads) void plane_segment_kernel(
             off += n;
         }
         plane_counts[f] = nk;
+        // a crossed limit, tagged with the call it belongs to (spslam_planes_status); within the limits nothing
+        if (S.misc[7]) ts[14] = ((long long)b.epoch << 8) | S.misc[7];
     }
     __syncthreads();
     const int nk = S.nkept, ng = S.misc[0];
@@ -1332,13 +1337,24 @@ size_t plane_segment_lds_bytes(const PlaneGeom& g, bool* in_lds) {
     return bits + (fits ? maps : 0);
 }
 
+// The instance plane_segment_launch runs: *in_lds (maps and 16-bit parents in LDS), *k row positions per lane of the
+// refinement scans (4 for W <= 256, 8 for W <= 512).  hipErrorInvalidValue for a cloud no instance takes.
+hipError_t plane_segment_shape(const PlaneGeom& g, int* in_lds, int* k) {
+    if (g.W > 64 * planes::kMaxRowWords || g.N >= (1 << 24)) return hipErrorInvalidValue;
+    bool fits = false;
+    const size_t dyn = plane_segment_lds_bytes(g, &fits);
+    if (sizeof(planes::SegShared) + dyn > (size_t)planes::kLdsBytes) return hipErrorInvalidValue;
+    if (in_lds) *in_lds = fits;
+    if (k) *k = g.W <= 256 ? 4 : 8;
+    return hipSuccess;
+}
+
 hipError_t plane_segment_launch(const PlaneGeom& g, const PlaneBuffers& b, int n, spslam_plane* planes,
                                 int* plane_counts, int planes_cap, int32_t* inliers, int32_t* contours,
                                 hipStream_t s) {
-    if (g.W > 64 * planes::kMaxRowWords || g.N >= (1 << 24)) return hipErrorInvalidValue;
-    bool in_lds = false;
-    const size_t dyn = plane_segment_lds_bytes(g, &in_lds);
-    if (sizeof(planes::SegShared) + dyn > (size_t)planes::kLdsBytes) return hipErrorInvalidValue;
+    int in_lds = 0, K = 0;
+    if (const hipError_t e = plane_segment_shape(g, &in_lds, &K); e != hipSuccess) return e;
+    const size_t dyn = plane_segment_lds_bytes(g, nullptr);
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(n), dim3(planes::kSegThreads), dyn, s, g, b, planes, plane_counts, planes_cap,
                            inliers, contours);
@@ -1351,12 +1367,11 @@ hipError_t plane_segment_launch(const PlaneGeom& g, const PlaneBuffers& b, int n
     static const hipError_t a8 = lds_attr((const void*)planes::plane_segment_kernel<true, 8>);
     (void)a4;
     (void)a8;
-    // lane positions per refinement row: 4 for W <= 256, 8 for W <= 512
     if (in_lds) {
-        if (g.W <= 256) launch(planes::plane_segment_kernel<true, 4>);
+        if (K == 4) launch(planes::plane_segment_kernel<true, 4>);
         else launch(planes::plane_segment_kernel<true, 8>);
     } else {
-        if (g.W <= 256) launch(planes::plane_segment_kernel<false, 4>);
+        if (K == 4) launch(planes::plane_segment_kernel<false, 4>);
         else launch(planes::plane_segment_kernel<false, 8>);
     }
     return hipGetLastError();

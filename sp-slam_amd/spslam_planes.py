@@ -34,7 +34,15 @@ spslam_gpu.EXPORTED += ["spslam_planes_configure", "spslam_planes_capacity", "sp
                         "spslam_planes_generate_from_boundaries",
                         "spslam_planes_generate_from_boundaries_batch_device", "spslam_supposed_debug",
                         "spslam_planes_select_cloud_set",
-                        "spslam_debug_plane_not_seen"]
+                        "spslam_debug_plane_not_seen", "spslam_planes_status", "spslam_debug_plane_launch_shape"]
+
+# spslam_planes_status flags: the per-frame limits an extraction crossed
+OVER_COMPONENTS, OVER_MODELS, OVER_KEPT = 1, 2, 4
+
+
+class PlaneLaunchShape(ctypes.Structure):
+    _fields_ = [("seg_maps_in_lds", ctypes.c_int32), ("seg_positions", ctypes.c_int32),
+                ("wave_count", ctypes.c_int32), ("one_workgroup", ctypes.c_int32), ("barrier_rows", ctypes.c_int32)]
 
 
 def _bind(lib):
@@ -54,6 +62,8 @@ def _bind(lib):
     lib.spslam_supposed_debug.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ip, vp, ctypes.c_int]
     lib.spslam_planes_select_cloud_set.argtypes = [vp, ctypes.c_int]
     lib.spslam_debug_plane_not_seen.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp]
+    lib.spslam_planes_status.argtypes = [vp, ctypes.c_int, ip]
+    lib.spslam_debug_plane_launch_shape.argtypes = [vp, ctypes.c_int, ctypes.POINTER(PlaneLaunchShape)]
 
 
 def plane_not_seen(ex: spslam_gpu.OrbExtractor, planes, coefs):
@@ -123,6 +133,18 @@ class PlaneExtractor:
         self.ex._check(self.ex.lib.spslam_planes_extract_batch_device(
             self.ex.ctx, depth_ptr, n_frames, frame_stride, stride, planes_ptr, counts_ptr, inliers_ptr,
             contours_ptr, stream or None))
+
+    def status(self, frame=0):
+        """OVER_* flags of the limits frame `frame` of the last extraction crossed (synchronise its stream first)."""
+        flags = ctypes.c_int(-1)
+        self.ex._check(self.ex.lib.spslam_planes_status(self.ex.ctx, frame, ctypes.byref(flags)))
+        return flags.value
+
+    def launch_shape(self, n_frames=1):
+        """Test hook: the kernels an extraction of n_frames frames launches, as a dict of PlaneLaunchShape's fields."""
+        sh = PlaneLaunchShape()
+        self.ex._check(self.ex.lib.spslam_debug_plane_launch_shape(self.ex.ctx, n_frames, ctypes.byref(sh)))
+        return {name: int(getattr(sh, name)) for name, _ in PlaneLaunchShape._fields_}
 
     def keep_labels(self, on=True):
         """Test hook: store the connected-component labels (debug(frame, 3)) on later extractions."""

@@ -8,8 +8,9 @@ inlier index lists and contours identical; plane coefficients within 1e-4.
 import numpy as np
 import pytest
 
+from plane_common import COEF_TOL, compare as _compare, oracle as _oracle, refine_path as _refine_path
+
 pytestmark = pytest.mark.gpu
-COEF_TOL = 1e-4
 
 
 @pytest.fixture(scope="module")
@@ -36,42 +37,6 @@ def depth_frames():
             _, d, _ = sc.render(sc.pose(fi), noise_seed=fi)
             out.append(oracle_planes.depth_to_float(d))
     return out
-
-
-def _oracle(depth, scale=1.0, min_size=500):
-    import oracle_planes
-    import synth
-    K = synth.TUM3
-    po = oracle_planes.PlaneOracle()
-    res = po.extract(depth, K["fx"] * scale, K["fy"] * scale, K["cx"] * scale, K["cy"] * scale, min_size=min_size)
-    return po, res
-
-
-def _compare(pe, depth, k, scale=1.0, min_size=500):
-    """Every stage and output of one frame against the oracle; returns (#planes, #models)."""
-    po, ro = _oracle(depth, scale, min_size)
-    rg = pe(depth)
-    assert np.array_equal(pe.debug(0, 0), po.cloud(), equal_nan=True), f"frame {k}: cloud"
-    assert np.array_equal(pe.debug(0, 2), po.distance(), equal_nan=True), f"frame {k}: distance map"
-    ng, no = pe.debug(0, 1), po.normals()
-    assert np.array_equal(np.isnan(ng), np.isnan(no)), f"frame {k}: normal validity"
-    m = ~np.isnan(no)
-    assert np.array_equal(ng[m], no[m]), f"frame {k}: normals"
-    assert np.array_equal(pe.debug(0, 3), po.labels(False)), f"frame {k}: CC labels"
-    assert len(rg["coef"]) == len(ro["coef"]), f"frame {k}: {len(rg['coef'])} vs {len(ro['coef'])} planes"
-    for j in range(len(ro["coef"])):
-        assert np.abs(rg["coef"][j] - ro["coef"][j]).max() <= COEF_TOL * max(1.0, abs(ro["coef"][j][3])), \
-            f"frame {k} plane {j}: {rg['coef'][j]} vs {ro['coef'][j]}"
-        assert np.array_equal(rg["coef"][j], ro["coef"][j]), f"frame {k} plane {j}: coef not bit-exact"
-        assert np.array_equal(rg["inliers"][j], ro["inliers"][j]), f"frame {k} plane {j}: inliers"
-        assert np.array_equal(rg["contour"][j], ro["contour"][j]), f"frame {k} plane {j}: contour"
-    return len(ro["coef"]), po.n_models
-
-
-def _refine_path(n_models):
-    """Which refinement the kernel takes (plane_segment.hip phase K): fast narrow (<= 14 models, 16-bit
-    descriptors), fast wide (<= 30, 32-bit descriptors) or the general 64-bit path."""
-    return "narrow" if n_models <= 14 else "wide" if n_models <= 30 else "general"
 
 
 def test_planes_many_models(ctx):
