@@ -240,6 +240,9 @@ void quadratic_form(const Edge& e, const double J[3][6], double He[21], double s
 // (optimization_algorithm_levenberg.cpp:110-127, linear_solver_dense.h:107-112); "never written" is pinned to zeros.
 // trials counts the call's LM trials (the test hook oracle_set_solve_fail_mask).
 int optimize(std::vector<Edge*>& active, SE3& T, const Cam& c, int iterations, double* xs, int& trials) {
+    // no edge at level 0: initializeOptimization(0) leaves the pose vertex out of the active set and optimize()
+    // returns at once ("0 vertices to optimize", sparse_optimizer.cpp:356-359) -- no iteration, no trial
+    if (active.empty()) return 0;
     LM lm;
     int its = 0;
     for (int it = 0; it < iterations; it++) {
@@ -384,6 +387,8 @@ extern "C" int ORACLE_ENTRY(oracle_pose_optimize)(const spslam_pose_problem* P, 
     }
     std::memcpy(out->Tcw, P->Tcw, sizeof out->Tcw);
     out->lm_iterations = 0;
+    out->trial_passes = 0;  // a device diagnostic: how the kernel batches the trials
+    out->trials = 0;
     if (nInitial < 3) { out->n_inliers = 0; for (int i = 0; i < P->n_planes; i++) plout[i] = 0; return 0; }
     const double angleInfo = 3282.8 / (cfg->angle_info * cfg->angle_info);
     const double disInfo = cfg->distance_info * cfg->distance_info;
@@ -445,5 +450,6 @@ extern "C" int ORACLE_ENTRY(oracle_pose_optimize)(const spslam_pose_problem* P, 
     out->Tcw[12] = 0.f; out->Tcw[13] = 0.f; out->Tcw[14] = 0.f; out->Tcw[15] = 1.f;
     out->n_inliers = nInitial - nBad;
     out->lm_iterations = total_its;
+    out->trials = trials;
     return out->n_inliers;
 }

@@ -62,6 +62,7 @@ def test_pose_bit_exact_to_oracle(gpu, problems):
             f"problem {k}: pose differs {pose_close(rg['Tcw'], ro['Tcw'])[1]}"
         assert int(rg["n_inliers"]) == int(ro["n_inliers"]), f"problem {k}"
         assert int(rg["lm_iterations"]) == int(ro["lm_iterations"]), f"problem {k}"
+        assert int(rg["trials"]) == int(ro["trials"]), f"problem {k}"
         assert np.array_equal(pog, poo), f"problem {k}: point outliers differ at {np.nonzero(pog != poo)[0][:10]}"
         assert np.array_equal(plog, ploo), f"problem {k}: plane outliers differ"
         # and the optimizer actually converged to the ground truth
@@ -173,6 +174,7 @@ def test_pose_failed_solve_keeps_previous_solution(gpu, problems, mask):
         tag = f"mask {mask:#x} problem {k}"
         assert np.array_equal(rg["Tcw"].view(np.uint32), ro["Tcw"].view(np.uint32)), tag
         assert int(rg["n_inliers"]) == int(ro["n_inliers"]) and int(rg["lm_iterations"]) == int(ro["lm_iterations"]), tag
+        assert int(rg["trials"]) == int(ro["trials"]), tag
         assert np.array_equal(pog, poo) and np.array_equal(plog, ploo), tag
 
 
