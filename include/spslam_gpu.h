@@ -784,6 +784,123 @@ int spslam_search_local_points_batch_device(spslam_ctx* ctx, int n_frames, const
                                             int32_t* d_match, int* d_nmatches, uint8_t* d_in_view,
                                             const int32_t* d_seen, void* hip_stream);
 
+/* ---------------------------------------------------------------- LocalMapping: Fuse search, map-point refresh
+ * The search half of ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>&
+ * vpMapPoints, float th) (src/ORBmatcher.cc:842-949) as LocalMapping::
+ * SearchInNeighbors calls it (src/LocalMapping.cc:466-546): per map point the
+ * pre-checks, the projection into pKF, KeyFrame::GetFeaturesInArea
+ * (src/KeyFrame.cc:586-625) and the best descriptor among the candidates that
+ * pass Fuse's level and chi-square tests.  The map mutation that follows
+ * (:951-971: Replace / AddObservation / AddMapPoint) stays with the caller, who
+ * walks the results in point order; the reference fuses point i exactly when
+ * best_dist <= TH_LOW (50), and d_nfused counts those.
+ * CONTRACT: a map point occurs at most once in a problem's point range; then
+ * the search of point i does not depend on the mutation done for the points
+ * before it, and one call is one parallel search over a snapshot of the map.
+ * The points are spslam_local_point records (the table SearchLocalPoints
+ * reads); the keyframe is one slot of the frame stage's batch layouts.  The
+ * caller's flag per point (isBad() || IsInKeyFrame(pKF), :849) skips it.
+ * KeyFrame's image bounds are ints (include/KeyFrame.h:198-201): the configured
+ * bounds are truncated as `mnMinX(F.mnMinX)` does. */
+typedef struct spslam_fuse_problem {
+    float Tcw[16];        /* pKF->GetPose(), row-major */
+    int32_t kf_slot;      /* the keyframe's arrays: keys_un / uright / grid_idx at kf_slot*cap, desc at kf_slot*cap*32,
+                             grid_off at kf_slot*(64*48+1), d_counts[kf_slot] keypoints */
+    int32_t point_offset; /* vpMapPoints: spslam_local_point records [point_offset, point_offset + n_points) */
+    int32_t n_points;
+    int32_t out_offset;   /* result and skip flag of point i at out_offset + i */
+} spslam_fuse_problem;    /* 80 bytes */
+
+#define SPSLAM_FUSE_SEARCHED 0       /* vIndices not empty: best_idx / best_dist hold the loop's result */
+#define SPSLAM_FUSE_SKIPPED 1        /* the caller's flag (:849) */
+#define SPSLAM_FUSE_BEHIND 2         /* p3Dc.z < 0 (:856) */
+#define SPSLAM_FUSE_OUTSIDE_IMAGE 3  /* !pKF->IsInImage(u, v) (:867), z == 0 included */
+#define SPSLAM_FUSE_OUT_OF_RANGE 4   /* dist3D outside the scale invariance region (:878) */
+#define SPSLAM_FUSE_VIEW_ANGLE 5     /* PO.dot(Pn) < 0.5 * dist3D (:884) */
+#define SPSLAM_FUSE_NO_CANDIDATES 6  /* vIndices.empty() (:894) */
+
+typedef struct spslam_fuse_result {
+    int32_t best_idx;     /* keypoint of pKF, -1 when no candidate passed */
+    int16_t best_dist;    /* 256 when none passed; the caller fuses when <= TH_LOW (50) */
+    uint8_t level;        /* nPredictedLevel (0 when PredictScale was not reached) */
+    uint8_t status;       /* SPSLAM_FUSE_* */
+} spslam_fuse_result;     /* 8 bytes */
+
+typedef struct spslam_fuse_params {
+    float th;             /* radius at level 0 (Fuse's default 3.0, include/ORBmatcher.h:80) */
+    int32_t pad;
+} spslam_fuse_params;
+
+/* Drop-in for one keyframe on host buffers: n_points points into the keyframe
+ * (keys_un / desc / uright: n_kp keypoints, grid_off (64*48+1) / grid_idx: its
+ * mGrid CSR).  skip: n_points flags, may be NULL.  results: n_points records;
+ * *nfused receives Fuse's return value. */
+int spslam_fuse_search(spslam_ctx* ctx, const float* Tcw, const spslam_local_point* points, int n_points,
+                       const spslam_keypoint* keys_un, const uint8_t* desc, const float* uright, int n_kp,
+                       const int32_t* grid_off, const int32_t* grid_idx, const uint8_t* skip,
+                       const spslam_fuse_params* params, spslam_fuse_result* results, int* nfused);
+
+/* Batched, device resident.  Problems may share a keyframe slot and may share
+ * a point range; only their [out_offset, out_offset + n_points) ranges must be
+ * disjoint.  d_skip (may be NULL) and d_results are indexed by out index;
+ * max_points bounds every problem's n_points (host-known launch size);
+ * d_nfused: one int per problem. */
+int spslam_fuse_search_batch_device(spslam_ctx* ctx, int n_problems, const spslam_fuse_problem* d_problems,
+                                    const spslam_local_point* d_points, int max_points,
+                                    const spslam_keypoint* d_keys_un, const uint8_t* d_desc, const float* d_uright,
+                                    const int32_t* d_grid_off, const int32_t* d_grid_idx, const int* d_counts,
+                                    int cap, const uint8_t* d_skip, const spslam_fuse_params* params,
+                                    spslam_fuse_result* d_results, int* d_nfused, void* hip_stream);
+
+/* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307) and
+ * MapPoint::UpdateNormalAndDepth (:330-371) for listed rows of the
+ * spslam_local_point table, in place: desc, normal, min_dist, max_dist are
+ * written; xw, id, n_obs and pad are not.  Several sequences' maps are packed
+ * by the caller with absolute offsets and indices (no batch dimension).
+ * Descriptor: observers in ascending keyframe order without those in bad
+ * keyframes; per observer the element floor(0.5*(N-1)) of its sorted N
+ * distances; the first observer with the strictly smallest one gives the
+ * descriptor; none left: unchanged.  Normal and depth: every observer (bad
+ * keyframes too: the reference does not check), float arithmetic, cv::norm
+ * with the squares accumulated in double.
+ * CONTRACT: a row occurs at most once in the row list. */
+#define SPSLAM_POINT_MAX_OBS 128     /* observers per point; more: SPSLAM_REFRESH_CAPACITY, the record untouched */
+#define SPSLAM_REFRESH_DESCRIPTOR 1
+#define SPSLAM_REFRESH_NORMAL_DEPTH 2
+#define SPSLAM_REFRESH_DONE 0
+#define SPSLAM_REFRESH_UNTOUCHED 1   /* a bad point or a point without observers: both functions return early */
+#define SPSLAM_REFRESH_CAPACITY 2
+
+typedef struct spslam_point_refresh_map {
+    const float* kf_Tcw;        /* n_kf * 16: KeyFrame::GetPose; the camera centre Ow = -Rcw^T tcw (KeyFrame.cc:82) is
+                                   made on the device: three products summed in double in row order, negated, rounded */
+    const int32_t* kf_slot;     /* n_kf: the keyframe's slot in d_keys_un (octave) / d_desc */
+    const uint8_t* kf_bad;      /* n_kf, may be NULL */
+    const int32_t* obs_off;     /* n_rows + 1 */
+    const int32_t* obs_kf;      /* per row ascending keyframe index (std::map<KeyFrame*> order) */
+    const int32_t* obs_kp;      /* that observation's keypoint index */
+    const int32_t* ref_kf;      /* n_rows: mpRefKF; not among the row's observers: the first observer */
+    const uint8_t* point_bad;   /* n_rows, may be NULL */
+    spslam_local_point* points; /* the table */
+} spslam_point_refresh_map;
+
+/* Device resident: map's pointers, d_rows (n table rows), d_keys_un / d_desc at
+ * slot*cap (the frame stage's layouts) and d_status (n, SPSLAM_REFRESH_*) are
+ * device memory; what: a mask of SPSLAM_REFRESH_DESCRIPTOR / _NORMAL_DEPTH.
+ * Scale factors and level count are the ORB tables'. */
+int spslam_map_points_refresh_batch_device(spslam_ctx* ctx, const spslam_point_refresh_map* map,
+                                           const int32_t* d_rows, int n, int what,
+                                           const spslam_keypoint* d_keys_un, const uint8_t* d_desc, int cap,
+                                           uint8_t* d_status, void* hip_stream);
+
+/* The same on host arrays (map's pointers too): n_kf keyframes, n_rows table
+ * rows, n_slots keyframe slots of cap keypoints.  map->points is rewritten in
+ * place.  Returns SPSLAM_ERR_CAPACITY when a row reported
+ * SPSLAM_REFRESH_CAPACITY (every other row is done and copied back). */
+int spslam_map_points_refresh(spslam_ctx* ctx, const spslam_point_refresh_map* map, int n_kf, int n_rows,
+                              const int32_t* rows, int n, int what, const spslam_keypoint* keys_un,
+                              const uint8_t* desc, int cap, int n_slots, uint8_t* status);
+
 /* ---------------------------------------------------------------- input images
  * Tracking::GrabImageRGBD's image preparation (src/Tracking.cc:208-229), the
  * first kernel of a step:

@@ -24,6 +24,7 @@
 #include "assoc_launch.h"
 #include "bow_launch.h"
 #include "match_launch.h"
+#include "map_point_launch.h"
 #include "track_launch.h"
 #include "grab_launch.h"
 

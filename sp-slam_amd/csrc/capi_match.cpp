@@ -1,4 +1,5 @@
-// C ABI (include/spslam_gpu.h): projection and local-point search, the tracking graph, masked copies and bag of words.
+// C ABI (include/spslam_gpu.h): projection, local-point and Fuse search, the map-point refresh, the tracking graph,
+// masked copies and bag of words.
 #include "capi_ctx.h"
 
 #include <cmath>
@@ -144,6 +145,150 @@ int spslam_search_local_points(spslam_ctx* c, const spslam_local_frame* frame, c
     if (in_view && np) HIP_CHECK(c, hipMemcpyAsync(in_view, st.slot<uint8_t>(11), (size_t)np, hipMemcpyDeviceToHost, c->stream));
     if ((rc = st.close())) return rc;
     HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+int spslam_fuse_search_batch_device(spslam_ctx* c, int n_problems, const spslam_fuse_problem* d_problems,
+                                    const spslam_local_point* d_points, int max_points,
+                                    const spslam_keypoint* d_keys_un, const uint8_t* d_desc, const float* d_uright,
+                                    const int32_t* d_grid_off, const int32_t* d_grid_idx, const int* d_counts,
+                                    int cap, const uint8_t* d_skip, const spslam_fuse_params* params,
+                                    spslam_fuse_result* d_results, int* d_nfused, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    if (n_problems < 1 || !d_problems || max_points < 0 || (max_points > 0 && (!d_points || !d_results)) ||
+        !d_keys_un || !d_desc || !d_uright || !d_grid_off || !d_grid_idx || !d_counts || cap < 1 ||
+        cap > (1 << 20) || !params || !d_nfused)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_fuse_search_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    // KeyFrame's mnMinX .. mnMaxY are ints initialised from the Frame's floats (KeyFrame.cc:41, KeyFrame.h:198-201)
+    MatchGeom g = match_geom(c);
+    g.min_x = (float)(int)g.min_x; g.max_x = (float)(int)g.max_x;
+    g.min_y = (float)(int)g.min_y; g.max_y = (float)(int)g.max_y;
+    FuseConsts P{};
+    P.th = params->th;
+    P.log_scale_factor = std::log(c->p.scale_factor);  // mfLogScaleFactor, float
+    P.n_levels = c->p.nlevels;
+    for (int l = 0; l < 8; l++) P.inv_sigma2[l] = l < c->p.nlevels ? c->inv_sigma2[l] : 0.f;
+    MatchCurrent cur{d_keys_un, d_desc, d_uright, d_grid_off, d_grid_idx, d_counts, cap};
+    HIP_CHECK(c, fuse_search_launch(n_problems, d_problems, d_points, max_points, cur, g, P, d_skip, d_results,
+                                    d_nfused, (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_fuse_search(spslam_ctx* c, const float* Tcw, const spslam_local_point* points, int n_points,
+                       const spslam_keypoint* keys_un, const uint8_t* desc, const float* uright, int n_kp,
+                       const int32_t* grid_off, const int32_t* grid_idx, const uint8_t* skip,
+                       const spslam_fuse_params* params, spslam_fuse_result* results, int* nfused) {
+    if (!c || !Tcw || !params || !grid_off || !nfused || n_kp < 0 || n_points < 0 ||
+        (n_points && (!points || !results)) || (n_kp && (!keys_un || !desc || !uright || !grid_idx)))
+        return SPSLAM_ERR_ARG;
+    constexpr int kCells = SPSLAM_GRID_COLS * SPSLAM_GRID_ROWS;
+    if (grid_off[0] != 0 || grid_off[kCells] > n_kp)
+        return fail(c, SPSLAM_ERR_ARG, "grid CSR does not fit the keypoints%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    spslam_fuse_problem F{};
+    std::memcpy(F.Tcw, Tcw, sizeof F.Tcw);
+    F.n_points = n_points;
+    const int np = n_points, cap = std::max(n_kp, 1);
+    const size_t K = (size_t)n_kp, C = (size_t)cap, N = (size_t)std::max(np, 1);
+    Stage st(c);
+    if (int rc = st.open({{&F, sizeof F}, {points, np * sizeof(spslam_local_point), N * sizeof(spslam_local_point)},
+                           {keys_un, K * sizeof(spslam_keypoint), C * sizeof(spslam_keypoint)},
+                           {desc, K * 32, C * 32}, {uright, K * 4, C * 4},
+                           {grid_off, (kCells + 1) * 4}, {grid_idx, (size_t)grid_off[kCells] * 4, C * 4},
+                           {&n_kp, sizeof(int)}, {skip, skip ? (size_t)np : 0, N},
+                           N * sizeof(spslam_fuse_result), sizeof(int)}))
+        return rc;
+    int rc = spslam_fuse_search_batch_device(
+        c, 1, st.slot<spslam_fuse_problem>(0), st.slot<spslam_local_point>(1), np, st.slot<spslam_keypoint>(2),
+        st.slot<uint8_t>(3), st.slot<float>(4), st.slot<int32_t>(5), st.slot<int32_t>(6), st.slot<int>(7), cap,
+        skip ? st.slot<uint8_t>(8) : nullptr, params, st.slot<spslam_fuse_result>(9), st.slot<int>(10), c->stream);
+    if (rc) return rc;
+    if (np)
+        HIP_CHECK(c, hipMemcpyAsync(results, st.slot<void>(9), (size_t)np * sizeof(spslam_fuse_result),
+                                    hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(nfused, st.slot<int>(10), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+int spslam_map_points_refresh_batch_device(spslam_ctx* c, const spslam_point_refresh_map* map, const int32_t* d_rows,
+                                           int n, int what, const spslam_keypoint* d_keys_un, const uint8_t* d_desc,
+                                           int cap, uint8_t* d_status, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    constexpr int kAll = SPSLAM_REFRESH_DESCRIPTOR | SPSLAM_REFRESH_NORMAL_DEPTH;
+    if (!map || n < 0 || (n && (!d_rows || !d_status)) || what < 1 || (what & ~kAll) || cap < 1 || cap > (1 << 20))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_map_points_refresh_batch_device");
+    const spslam_point_refresh_map& m = *map;
+    if (!m.obs_off || !m.obs_kf || !m.obs_kp || !m.kf_slot || !m.points ||
+        ((what & SPSLAM_REFRESH_DESCRIPTOR) && !d_desc) ||
+        ((what & SPSLAM_REFRESH_NORMAL_DEPTH) && (!m.kf_Tcw || !m.ref_kf || !d_keys_un)))
+        return fail(c, SPSLAM_ERR_ARG, "missing buffer for spslam_map_points_refresh_batch_device%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    RefreshConsts P{};
+    P.n_levels = c->p.nlevels;
+    for (int l = 0; l < 8; l++) P.scale[l] = l < c->p.nlevels ? c->scale[l] : 0.f;
+    HIP_CHECK(c, map_points_refresh_launch(m, d_rows, n, what, d_keys_un, d_desc, cap, P, d_status,
+                                           (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_map_points_refresh(spslam_ctx* c, const spslam_point_refresh_map* map, int n_kf, int n_rows,
+                              const int32_t* rows, int n, int what, const spslam_keypoint* keys_un,
+                              const uint8_t* desc, int cap, int n_slots, uint8_t* status) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!map || n_kf < 0 || n_rows < 0 || n < 0 || (n && (!rows || !status)) || cap < 1 || n_slots < 0 ||
+        !map->obs_off || (n_rows && !map->points) || (n_kf && (!map->kf_Tcw || !map->kf_slot)) ||
+        (n_rows && !map->ref_kf) || ((size_t)n_slots * cap && (!keys_un || !desc)))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_map_points_refresh");
+    const spslam_point_refresh_map& m = *map;
+    const int n_obs = m.obs_off[n_rows];
+    if (m.obs_off[0] != 0 || n_obs < 0 || (n_obs && (!m.obs_kf || !m.obs_kp)))
+        return fail(c, SPSLAM_ERR_ARG, "spslam_map_points_refresh: the CSR does not start at 0 or lacks its arrays%s", "");
+    // every index the kernel follows, checked here: the device form trusts its tables
+    bool ok = true;
+    for (int r = 0; r < n_rows; r++) ok = ok && m.obs_off[r] <= m.obs_off[r + 1];
+    for (int k = 0; k < n; k++) ok = ok && rows[k] >= 0 && rows[k] < n_rows;
+    for (int k = 0; k < n_kf; k++) ok = ok && m.kf_slot[k] >= 0 && m.kf_slot[k] < n_slots;
+    for (int o = 0; o < n_obs && ok; o++)
+        ok = m.obs_kf[o] >= 0 && m.obs_kf[o] < n_kf && m.obs_kp[o] >= 0 && m.obs_kp[o] < cap;
+    if (!ok) return fail(c, SPSLAM_ERR_ARG, "spslam_map_points_refresh: an index outside its table%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const size_t R = (size_t)n_rows, K = (size_t)n_kf, O = (size_t)n_obs, S = (size_t)n_slots * cap,
+                 Pt = sizeof(spslam_local_point), Kp = sizeof(spslam_keypoint);
+    const auto one = [](size_t x) { return std::max(x, (size_t)1); };
+    Stage st(c);
+    if (int rc = st.open({{m.kf_Tcw, K * 64, one(K) * 64}, {m.kf_slot, K * 4, one(K) * 4},
+                           {m.kf_bad, m.kf_bad ? K : 0, one(K)}, {m.obs_off, (R + 1) * 4},
+                           {m.obs_kf, O * 4, one(O) * 4}, {m.obs_kp, O * 4, one(O) * 4},
+                           {m.ref_kf, R * 4, one(R) * 4}, {m.point_bad, m.point_bad ? R : 0, one(R)},
+                           {m.points, R * Pt, one(R) * Pt}, {rows, (size_t)n * 4, one((size_t)n) * 4},
+                           {keys_un, S * Kp, one(S) * Kp}, {desc, S * 32, one(S) * 32}, one((size_t)n)}))
+        return rc;
+    spslam_point_refresh_map dm{};
+    dm.kf_Tcw = st.slot<float>(0);
+    dm.kf_slot = st.slot<int32_t>(1);
+    dm.kf_bad = m.kf_bad ? st.slot<uint8_t>(2) : nullptr;
+    dm.obs_off = st.slot<int32_t>(3);
+    dm.obs_kf = st.slot<int32_t>(4);
+    dm.obs_kp = st.slot<int32_t>(5);
+    dm.ref_kf = st.slot<int32_t>(6);
+    dm.point_bad = m.point_bad ? st.slot<uint8_t>(7) : nullptr;
+    dm.points = st.slot<spslam_local_point>(8);
+    int rc = spslam_map_points_refresh_batch_device(c, &dm, st.slot<int32_t>(9), n, what, st.slot<spslam_keypoint>(10),
+                                                    st.slot<uint8_t>(11), cap, st.slot<uint8_t>(12), c->stream);
+    if (rc) return rc;
+    if (n) {
+        HIP_CHECK(c, hipMemcpyAsync(m.points, dm.points, R * Pt, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(c, hipMemcpyAsync(status, st.slot<uint8_t>(12), (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    }
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < n; k++)
+        if (status[k] == SPSLAM_REFRESH_CAPACITY)
+            return fail(c, SPSLAM_ERR_CAPACITY, "spslam_map_points_refresh: a row has more than %s observers", "128");
     return SPSLAM_OK;
 }
 

@@ -21,6 +21,8 @@
 //                        cooperatively (64 lanes, min over keys) excluding the
 //                        taken keypoints (LDS bitmap); then the rotation
 //                        histogram check.
+//   fuse_search_kernel   ORBmatcher::Fuse(pKF, vpMapPoints, th), the search (:842-949): the window kernel's
+//                        shape, 4 lanes per point, with Fuse's own candidate test; no in-order walk (below).
 // Float expressions follow the reference build's contraction pattern; the
 // cv::Mat products are accumulated in double and rounded once (oracle header).
 #include <hip/hip_runtime.h>
@@ -733,6 +735,125 @@ __global__ __launch_bounds__(64) void local_assign_kernel(const spslam_local_fra
 #endif
 }
 
+// ---------------------------------------------------------------------------
+// ORBmatcher::Fuse(pKF, vpMapPoints, th), the search (src/ORBmatcher.cc:842-949): one point per kLGrp lanes, no
+// in-order walk -- with every point at most once in the list the search of point i does not depend on the map
+// mutation (:951-971) of the points before it (include/spslam_gpu.h), so the kernel is the window kernel alone.
+// Its float expressions are Fuse's own, with the contractions GCC emits for them (tests/test_fuse_host.py).
+constexpr int kFusePtsPerBlock = kThreads / kLGrp;
+constexpr int kThLow = 50;
+
+struct FuseProbe {
+    float u, v, ur, r;
+    int level;
+    uint4 d0, d1;
+};
+
+// Fuse's loop body for keypoint k at CSR position j (:903-949): the key, or kNone when the keypoint is not in
+// vIndices or fails the level or chi-square test; *in_area: it is in vIndices (KeyFrame::GetFeaturesInArea's test).
+__device__ __forceinline__ uint32_t fuse_candidate_key(const FuseProbe& p, const FrameView& V, const FuseConsts& P,
+                                                       int j, int k, bool* in_area) {
+    const spslam_keypoint kp = V.kun[k];
+    const float dx = __fsub_rn(kp.x, p.u), dy = __fsub_rn(kp.y, p.v);
+    if (!(fabsf(dx) < p.r && fabsf(dy) < p.r)) return kNone;
+    *in_area = true;
+    if (kp.octave < p.level - 1 || kp.octave > p.level) return kNone;
+    const float ex = __fsub_rn(p.u, kp.x), ey = __fsub_rn(p.v, kp.y);
+    float e2 = __fmaf_rn(ex, ex, __fmul_rn(ey, ey));  // ex*ex+ey*ey
+    const float kpr = V.uright[k];
+    double limit = 5.99;
+    if (kpr >= 0) {  // the stereo branch: >= 0 here, 0.0f included (:914)
+        const float er = __fsub_rn(p.ur, kpr);
+        e2 = __fmaf_rn(er, er, e2);  // ex*ex+ey*ey+er*er
+        limit = 7.8;
+    }
+    if ((double)__fmul_rn(e2, level_entry(P.inv_sigma2, kp.octave)) > limit) return kNone;
+    return ((uint32_t)hamming(p.d0, p.d1, V.desc + 32 * (size_t)k) << 20) | (uint32_t)j;
+}
+
+// One point: the status; *level once PredictScale is reached; *best the smallest key, in every lane of the point.
+// Every return is uniform over the point's lanes.
+__device__ __forceinline__ int fuse_point(const spslam_fuse_problem& F, const spslam_local_point& p,
+                                          const MatchCurrent& C, const MatchGeom& g, const FuseConsts& P, int sub,
+                                          int* level, uint32_t* best) {
+    const float tcw[3] = {F.Tcw[3], F.Tcw[7], F.Tcw[11]};
+    float Pc[3], Ow[3];
+    mat3_mul(F.Tcw, p.xw, tcw, false, 1.0, Pc);  // Rcw*p3Dw + tcw
+    if (Pc[2] < 0.0f) return SPSLAM_FUSE_BEHIND;
+    const float invz = __fdiv_rn(1.0f, Pc[2]);
+    const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
+    const float u = __fmaf_rn(g.fx, x, g.cx), v = __fmaf_rn(g.fy, y, g.cy);  // fx*x+cx (:863)
+    // KeyFrame::IsInImage: half open (KeyFrame.cc:627-630); z == 0 makes u / v inf or NaN, which fail it
+    if (!(u >= g.min_x && u < g.max_x && v >= g.min_y && v < g.max_y)) return SPSLAM_FUSE_OUTSIDE_IMAGE;
+    const float ur = __fmaf_rn(-g.bf, invz, u);  // u-bf*invz (:870)
+    const float maxD = __fmul_rn(1.2f, p.max_dist), minD = __fmul_rn(0.8f, p.min_dist);
+    mat3_mul(F.Tcw, tcw, nullptr, true, -1.0, Ow);
+    const float PO[3] = {__fsub_rn(p.xw[0], Ow[0]), __fsub_rn(p.xw[1], Ow[1]), __fsub_rn(p.xw[2], Ow[2])};
+    float sq = __fmul_rn(PO[0], PO[0]);
+    sq = __fadd_rn(sq, __fmul_rn(PO[1], PO[1]));
+    sq = __fadd_rn(sq, __fmul_rn(PO[2], PO[2]));
+    const float dist = (float)__dsqrt_rn((double)sq);  // cv::norm, local_window_kernel's reading
+    if (dist < minD || dist > maxD) return SPSLAM_FUSE_OUT_OF_RANGE;
+    double dot = __dmul_rn((double)PO[0], (double)p.normal[0]);
+    dot = __dadd_rn(dot, __dmul_rn((double)PO[1], (double)p.normal[1]));
+    dot = __dadd_rn(dot, __dmul_rn((double)PO[2], (double)p.normal[2]));
+    if (dot < __dmul_rn(0.5, (double)dist)) return SPSLAM_FUSE_VIEW_ANGLE;  // doubles, no division (:884)
+    // PredictScale(dist3D, pKF), as local_window_kernel has it
+    const float ratio = __fdiv_rn(p.max_dist, dist);
+    const int n = (int)ceilf(__fdiv_rn((float)log((double)ratio), P.log_scale_factor));
+    *level = n < 0 ? 0 : (n >= P.n_levels ? P.n_levels - 1 : n);
+    const FuseProbe q{u, v, ur, __fmul_rn(P.th, level_entry(g.scale, *level)), *level,
+                      *(const uint4*)p.desc, *(const uint4*)(p.desc + 16)};
+    int x0, x1, y0, y1;
+    if (!cell_range(u, v, q.r, g, &x0, &x1, &y0, &y1)) return SPSLAM_FUSE_NO_CANDIDATES;
+    // the window's cells (column-major, as KeyFrame::GetFeaturesInArea scans them) dealt to the point's lanes
+    const FrameView V = frame_view(C, F.kf_slot);
+    uint32_t bk[1] = {kNone};
+    bool any = false;
+    const int nrows = y1 - y0 + 1, ncells = (x1 - x0 + 1) * nrows;
+    for (int cell = sub; cell < ncells; cell += kLGrp) {
+        const int cx = cell / nrows, c = (x0 + cx) * kRows + y0 + (cell - cx * nrows);
+        const int j0 = V.GO[c], j1 = V.GO[c + 1];
+        for (int j = j0; j < j1; j++) insk(bk, fuse_candidate_key(q, V, P, j, V.GI[j], &any));
+    }
+    int anyi = any;
+#pragma unroll
+    for (int o = kLGrp / 2; o >= 1; o >>= 1) {
+        insk(bk, (uint32_t)__shfl_xor((int)bk[0], o));
+        anyi |= __shfl_xor(anyi, o);
+    }
+    *best = bk[0];
+    return anyi ? SPSLAM_FUSE_SEARCHED : SPSLAM_FUSE_NO_CANDIDATES;
+}
+
+__global__ __launch_bounds__(kThreads) void fuse_search_kernel(const spslam_fuse_problem* __restrict__ problems,
+                                                               const spslam_local_point* __restrict__ points,
+                                                               int max_points, MatchCurrent C, MatchGeom g,
+                                                               FuseConsts P, const uint8_t* __restrict__ skip,
+                                                               spslam_fuse_result* __restrict__ results,
+                                                               int* __restrict__ nfused) {
+    const int f = blockIdx.x, sub = threadIdx.x & (kLGrp - 1);
+    const int i = blockIdx.y * kFusePtsPerBlock + (int)(threadIdx.x / kLGrp);
+    const spslam_fuse_problem& F = problems[f];
+    const bool live = i < F.n_points && i < max_points;  // uniform over the point's lanes
+    int status = SPSLAM_FUSE_SKIPPED, level = 0;
+    uint32_t best = kNone;
+    if (live && !(skip && skip[F.out_offset + i]))
+        status = fuse_point(F, points[F.point_offset + i], C, g, P, sub, &level, &best);
+    const int dist = best != kNone ? (int)(best >> 20) : 256;
+    if (live && sub == 0) {
+        spslam_fuse_result r;
+        r.best_idx = best != kNone ? frame_view(C, F.kf_slot).GI[best & 0xfffff] : -1;
+        r.best_dist = (int16_t)dist;
+        r.level = (uint8_t)level;
+        r.status = (uint8_t)status;
+        results[F.out_offset + i] = r;
+    }
+    // nFused: the points with bestDist <= TH_LOW (:952), one atomic per wave that has any
+    const int n = wave_sum(live && sub == 0 && dist <= kThLow);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&nfused[f], n);
+}
+
 }  // namespace match
 
 // Dynamic LDS beyond the default 64 KB needs the per-kernel opt-in: both instantiations (K keys per point) of a walk.
@@ -764,6 +885,19 @@ hipError_t local_match_launch(int n_frames, const spslam_local_frame* frames, co
     if (n_frames <= kSmallBatchKeys) run(win);
     else run(reinterpret_cast<LocalWindowK<kFewKeys>*>(win));
     if (timer) timer->end(kKindLocalMatch, s);
+    return hipGetLastError();
+}
+
+hipError_t fuse_search_launch(int n_problems, const spslam_fuse_problem* problems, const spslam_local_point* points,
+                              int max_points, const MatchCurrent& cur, const MatchGeom& g, const FuseConsts& P,
+                              const uint8_t* skip, spslam_fuse_result* results, int* nfused, hipStream_t s) {
+    if (n_problems < 1 || max_points < 0 || cur.cap < 1) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(nfused, 0, (size_t)n_problems * sizeof(int), s);
+    if (e != hipSuccess) return e;
+    if (max_points > 0)
+        hipLaunchKernelGGL(match::fuse_search_kernel,
+                           dim3(n_problems, (max_points + match::kFusePtsPerBlock - 1) / match::kFusePtsPerBlock),
+                           dim3(match::kThreads), 0, s, problems, points, max_points, cur, g, P, skip, results, nfused);
     return hipGetLastError();
 }
 

@@ -65,6 +65,17 @@ hipError_t local_match_launch(int n_frames, const spslam_local_frame* frames, co
                               const uint8_t* taken_in, LocalWindow* win, int32_t* match, int* nmatches,
                               uint8_t* in_view, hipStream_t s, KernelTimer* timer);
 
+// ORBmatcher::Fuse's search (fuse_search_kernel).  g: the KeyFrame's geometry, its bounds truncated to ints.
+struct FuseConsts {
+    float th, log_scale_factor;
+    int n_levels;
+    float inv_sigma2[8];  // mvInvLevelSigma2
+};
+
+hipError_t fuse_search_launch(int n_problems, const spslam_fuse_problem* problems, const spslam_local_point* points,
+                              int max_points, const MatchCurrent& cur, const MatchGeom& g, const FuseConsts& P,
+                              const uint8_t* skip, spslam_fuse_result* results, int* nfused, hipStream_t s);
+
 hipError_t match_launch(int n_frames, const spslam_proj_frame* frames, const spslam_proj_point* points,
                         int max_points, const MatchCurrent& cur, const MatchGeom& g, const spslam_match_params& P,
                         MatchWindow* win, int2* pushes, int32_t* match, int* nmatches, hipStream_t s,

@@ -19,6 +19,14 @@ __device__ __forceinline__ int hamming(const uint4& a0, const uint4& a1, const u
     return hamming(a0, a1, *(const uint4*)b, *(const uint4*)(b + 16));
 }
 
+// l-th entry of a per-level table held in kernel arguments (a select chain: no indexed copy of the table)
+__device__ __forceinline__ float level_entry(const float (&t)[8], int l) {
+    float x = t[0];
+#pragma unroll
+    for (int q = 1; q < 8; q++) x = l == q ? t[q] : x;
+    return x;
+}
+
 // the rotation histogram's bin of a match: rot = a - b (+ 360 if negative), round(rot * factor), kHisto -> 0
 __device__ __forceinline__ int rotation_bin(float a, float b) {
     const float factor = 1.0f / kHisto;

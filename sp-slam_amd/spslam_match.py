@@ -122,3 +122,113 @@ class LocalMatcher:
             self.ex.ctx, n_frames, d_frames, d_points, max_points, d_keys_un, d_desc, d_uright, d_grid_off,
             d_grid_idx, d_counts, cap, d_taken or None, ctypes.byref(self.params), d_match, d_nmatches,
             d_in_view or None, d_seen or None, stream or None))
+
+
+# ---------------------------------------------------------------- LocalMapping: Fuse search, map-point refresh
+FUSE_PROBLEM_DTYPE = np.dtype([("Tcw", "<f4", 16), ("kf_slot", "<i4"), ("point_offset", "<i4"), ("n_points", "<i4"),
+                               ("out_offset", "<i4")])
+assert FUSE_PROBLEM_DTYPE.itemsize == 80
+FUSE_RESULT_DTYPE = np.dtype([("best_idx", "<i4"), ("best_dist", "<i2"), ("level", "u1"), ("status", "u1")])
+assert FUSE_RESULT_DTYPE.itemsize == 8
+FUSE_SEARCHED, FUSE_SKIPPED, FUSE_BEHIND, FUSE_OUTSIDE_IMAGE, FUSE_OUT_OF_RANGE, FUSE_VIEW_ANGLE, \
+    FUSE_NO_CANDIDATES = range(7)
+TH_LOW = 50
+
+
+class FuseParams(ctypes.Structure):
+    _fields_ = [("th", ctypes.c_float), ("pad", ctypes.c_int)]
+
+
+# LocalMapping::SearchInNeighbors: matcher.Fuse(pKFi, vpMapPointMatches) with the default th = 3.0
+FUSE = (3.0, 0)
+
+spslam_gpu.EXPORTED += ["spslam_fuse_search", "spslam_fuse_search_batch_device"]
+
+
+class FuseSearch:
+    """GPU search of ORBmatcher::Fuse(pKF, vpMapPoints, th) on a context configured with spslam_frame_configure;
+    the map mutation (Replace / AddObservation) stays with the caller."""
+
+    def __init__(self, ex: spslam_gpu.OrbExtractor, params=FUSE):
+        self.ex = ex
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        ex.lib.spslam_fuse_search.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        ex.lib.spslam_fuse_search_batch_device.argtypes = [vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp,
+                                                           vp, vp]
+        self.params = FuseParams(*params)
+
+    def __call__(self, Tcw, points, keys_un, desc, uright, grid_off, grid_idx, skip=None):
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        pts = np.ascontiguousarray(points, LOCAL_POINT_DTYPE)
+        k = np.ascontiguousarray(keys_un, spslam_gpu.KEYPOINT_DTYPE)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        ur = np.ascontiguousarray(uright, np.float32)
+        go = np.ascontiguousarray(grid_off, np.int32)
+        gi = np.ascontiguousarray(grid_idx, np.int32)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        res = np.zeros(max(len(pts), 1), FUSE_RESULT_DTYPE)
+        nf = ctypes.c_int(0)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self.ex._check(self.ex.lib.spslam_fuse_search(
+            self.ex.ctx, T.ctypes.data, ptr(pts), len(pts), ptr(k), ptr(d), ptr(ur), len(k), go.ctypes.data, ptr(gi),
+            ptr(sk), ctypes.byref(self.params), res.ctypes.data, ctypes.byref(nf)))
+        return res[:len(pts)], nf.value
+
+    def batch_device(self, n_problems, d_problems, d_points, max_points, d_keys_un, d_desc, d_uright, d_grid_off,
+                     d_grid_idx, d_counts, cap, d_skip, d_results, d_nfused, stream=0):
+        self.ex._check(self.ex.lib.spslam_fuse_search_batch_device(
+            self.ex.ctx, n_problems, d_problems, d_points, max_points, d_keys_un, d_desc, d_uright, d_grid_off,
+            d_grid_idx, d_counts, cap, d_skip or None, ctypes.byref(self.params), d_results, d_nfused,
+            stream or None))
+
+
+POINT_MAX_OBS = 128
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
+REFRESH_DONE, REFRESH_UNTOUCHED, REFRESH_CAPACITY = 0, 1, 2
+ERR_CAPACITY = -2
+# the tables of spslam_point_refresh_map before `points`, in its order
+REFRESH_MAP_TABLES = (("kf_Tcw", np.float32), ("kf_slot", np.int32), ("kf_bad", np.uint8), ("obs_off", np.int32),
+                      ("obs_kf", np.int32), ("obs_kp", np.int32), ("ref_kf", np.int32), ("point_bad", np.uint8))
+
+
+class PointRefreshMap(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _ in REFRESH_MAP_TABLES] + [("points", ctypes.c_void_p)]
+
+
+spslam_gpu.EXPORTED += ["spslam_map_points_refresh", "spslam_map_points_refresh_batch_device"]
+
+
+class PointRefresh:
+    """GPU MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth on rows of the local-point table."""
+
+    def __init__(self, ex: spslam_gpu.OrbExtractor):
+        self.ex = ex
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        ex.lib.spslam_map_points_refresh.argtypes = [vp, vp, ci, ci, vp, ci, ci, vp, vp, ci, ci, vp]
+        ex.lib.spslam_map_points_refresh_batch_device.argtypes = [vp, vp, vp, ci, ci, vp, vp, ci, vp, vp]
+
+    def __call__(self, tables, points, rows, what, keys_un, desc, cap):
+        """tables: the REFRESH_MAP_TABLES arrays by name (kf_bad / point_bad may be None); points: the table, a copy
+        of which is refreshed and returned with the status per listed row and the return code (0, or ERR_CAPACITY
+        with every other row done)."""
+        a = {name: None if tables.get(name) is None else np.ascontiguousarray(tables[name], dt).reshape(-1)
+             for name, dt in REFRESH_MAP_TABLES}
+        pts = np.array(points, LOCAL_POINT_DTYPE)
+        rw = np.ascontiguousarray(rows, np.int32)
+        k = np.ascontiguousarray(keys_un, spslam_gpu.KEYPOINT_DTYPE).reshape(-1)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        assert len(k) % cap == 0 and len(d) == len(k)
+        status = np.full(max(len(rw), 1), 0xEE, np.uint8)
+        ptr = lambda x: x.ctypes.data if x is not None and x.size else None  # noqa: E731
+        m = PointRefreshMap(points=ptr(pts), **{name: ptr(a[name]) for name, _ in REFRESH_MAP_TABLES})
+        rc = self.ex.lib.spslam_map_points_refresh(self.ex.ctx, ctypes.byref(m), len(a["kf_slot"]), len(pts), ptr(rw),
+                                                   len(rw), what, ptr(k), ptr(d), cap, len(k) // cap,
+                                                   status.ctypes.data)
+        if rc != ERR_CAPACITY:
+            self.ex._check(rc)
+        return pts, status[:len(rw)], rc
+
+    def batch_device(self, refresh_map: PointRefreshMap, d_rows, n, what, d_keys_un, d_desc, cap, d_status, stream=0):
+        self.ex._check(self.ex.lib.spslam_map_points_refresh_batch_device(
+            self.ex.ctx, ctypes.byref(refresh_map), d_rows, n, what, d_keys_un or None, d_desc or None, cap, d_status,
+            stream or None))
