@@ -901,6 +901,138 @@ int spslam_map_points_refresh(spslam_ctx* ctx, const spslam_point_refresh_map* m
                               const int32_t* rows, int n, int what, const spslam_keypoint* keys_un,
                               const uint8_t* desc, int cap, int n_slots, uint8_t* status);
 
+/* ---------------------------------------------------------------- LocalMapping: CreateNewMapPoints
+ * LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:219-464) for RGB-D:
+ * ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:657-823 with
+ * CheckDistEpipolarLine :140-157) and the per-match triangulation and checks
+ * (:298-443).  One pair is (current keyframe, one neighbour).  The map mutation
+ * (new MapPoint, AddObservation, AddMapPoint, the refresh :447-459) stays with
+ * the caller, who walks the records in idx1 order; the device only marks the
+ * has-point bytes so that the next neighbour's search skips what this one took.
+ * F12 (ComputeF12, :548-565) is an input, as it is of SearchForTriangulation.
+ * Camera, bf, mb = bf/fx, the scale factors and mvLevelSigma2 are the context's
+ * (spslam_frame_configure); both keyframes share them (the reference reads the
+ * current keyframe's mbf for the neighbour's right-image error, :418).
+ * vbMatched2 of the reference is never written, so every key-1 feature is
+ * searched on its own: it keeps the candidate of smallest distance among those
+ * that pass every test, the later one in the node's list on a tie.
+ * The 4x4 cv::SVD of :342 is not vendored with the reference; the null vector
+ * here is a one-sided Jacobi with fixed order and double accumulators
+ * (DESIGN.md 3.14), not bit-pinned to any OpenCV build.
+ * PRECONDITIONS: uright[i] >= 0 implies depth[i] > 0 (KeyFrame::UnprojectStereo
+ * returns an empty Mat otherwise and the reference reads it).  A FeatureVector
+ * lists a feature in at most one node, as DBoW2 makes it, so that it holds at
+ * most `counts` entries; of a malformed one that lists more than cap entries
+ * the search takes cap of them and drops the rest without an error. */
+typedef struct spslam_tri_side {     /* frame-stage / bow batch layouts, slot s at s*cap (fv_start at s*(cap+1)) */
+    const spslam_keypoint* keys;     /* mvKeys   (UnprojectStereo) */
+    const spslam_keypoint* keys_un;  /* mvKeysUn */
+    const float* uright;
+    const float* depth;
+    const uint8_t* desc;             /* s*cap*32 */
+    uint8_t* has_point;              /* GetMapPoint(i) != NULL; written when mark != 0 */
+    const int* counts;
+    const uint32_t* fv_nodes;
+    const int32_t* fv_start;
+    const int32_t* fv_features;
+    const int* n_fv;
+    int32_t cap;                     /* 1 .. 8192 */
+    int32_t pad;
+} spslam_tri_side;
+
+typedef struct spslam_tri_pair {     /* one (current keyframe, neighbour) */
+    int32_t kf1, kf2;                /* slots */
+    float Tcw1[12], Tcw2[12];        /* [R | t], 3x4 row-major */
+    float Ow1[3], Ow2[3];            /* GetCameraCenter() */
+    float F12[9];
+    int32_t out_offset;              /* records; match12 at the same offset */
+    int32_t flags;                   /* bit 0: skip (caller's baseline / CheckNewKeyFrames decision) */
+} spslam_tri_pair;                   /* 172 bytes */
+#define SPSLAM_TRI_PAIR_SKIP 1
+
+#define SPSLAM_TRI_NEW 0             /* triangulation is successful (:443): the caller creates the MapPoint */
+#define SPSLAM_TRI_NO_MATCH 1        /* match12 < 0 */
+#define SPSLAM_TRI_LOW_PARALLAX 2    /* no stereo and very low parallax (:360) */
+#define SPSLAM_TRI_W_ZERO 3          /* x3D(3) == 0 (:345) */
+#define SPSLAM_TRI_BEHIND_1 4        /* z1 <= 0 (:367) */
+#define SPSLAM_TRI_BEHIND_2 5        /* z2 <= 0 (:371) */
+#define SPSLAM_TRI_REPROJ_1 6        /* 5.991 / 7.8 sigma2 in the current keyframe (:386, :397) */
+#define SPSLAM_TRI_REPROJ_2 7        /* the same in the neighbour (:412, :423) */
+#define SPSLAM_TRI_ZERO_DIST 8       /* dist1 == 0 || dist2 == 0 (:433) */
+#define SPSLAM_TRI_SCALE 9           /* scale consistency (:441) */
+#define SPSLAM_TRI_FROM_SVD 0
+#define SPSLAM_TRI_FROM_STEREO_1 1
+#define SPSLAM_TRI_FROM_STEREO_2 2
+
+typedef struct spslam_tri_result {
+    float x, y, z;        /* x3D at the exit (0 where none was made) */
+    int32_t idx2;         /* match12 of this key-1 feature */
+    uint8_t status;       /* SPSLAM_TRI_* */
+    uint8_t source;       /* SPSLAM_TRI_FROM_* */
+    uint16_t pad;
+} spslam_tri_result;      /* 20 bytes */
+
+#define SPSLAM_TRI_PAIR_SEARCHED 0
+#define SPSLAM_TRI_PAIR_SKIPPED 1          /* flags bit 0 */
+#define SPSLAM_TRI_PAIR_SHORT_BASELINE 2   /* baseline < mb (:263) */
+
+/* Batched, device resident.  Pair p writes match12 of key-1 feature i < counts[kf1]
+ * at d_match12[out_offset + i] (-1: none) and d_nmatches[p]; nothing else is
+ * written.  A pair with the skip flag gives -1 everywhere and 0.  The out ranges
+ * of the pairs must be disjoint; the pairs may share slots (nothing is marked). */
+int spslam_search_for_triangulation_batch_device(spslam_ctx* ctx, int n_pairs, const spslam_tri_pair* d_pairs,
+                                                 const spslam_tri_side* side, int only_stereo,
+                                                 int check_orientation, int32_t* d_match12, int* d_nmatches,
+                                                 void* hip_stream);
+
+/* One record per key-1 feature at d_results[out_offset + i], d_n_new[p] = the
+ * number of SPSLAM_TRI_NEW.  mark != 0: has_point[idx1] of kf1 and
+ * has_point[idx2] of kf2 are set to 1 for every SPSLAM_TRI_NEW record; then
+ * the pairs of one call must not share a keyframe slot. */
+int spslam_triangulate_batch_device(spslam_ctx* ctx, int n_pairs, const spslam_tri_pair* d_pairs,
+                                    const spslam_tri_side* side, const int32_t* d_match12, int mark,
+                                    spslam_tri_result* d_results, int* d_n_new, void* hip_stream);
+
+/* One neighbour round of CreateNewMapPoints for n_pairs sequences: the baseline
+ * test (:258-264, from Ow1 / Ow2), the search (ORBmatcher(0.6, false): both
+ * stereo and mono, no orientation check) and the triangulation with mark = 1.
+ * d_pair_status[p]: SPSLAM_TRI_PAIR_*; a pair that is not SEARCHED gives
+ * SPSLAM_TRI_NO_MATCH records.  RULE: the pairs of one call must not share a
+ * keyframe slot.  Calls on one stream are ordered, so round i+1 sees round i's
+ * marks without a host round trip. */
+int spslam_create_new_points_batch_device(spslam_ctx* ctx, int n_pairs, const spslam_tri_pair* d_pairs,
+                                          const spslam_tri_side* side, int32_t* d_match12, int* d_nmatches,
+                                          spslam_tri_result* d_results, int* d_n_new, uint8_t* d_pair_status,
+                                          void* hip_stream);
+
+/* Host arrays of one keyframe for the drop-ins below. */
+typedef struct spslam_tri_keyframe {
+    const spslam_keypoint* keys;
+    const spslam_keypoint* keys_un;
+    const float* uright;
+    const float* depth;
+    const uint8_t* desc;
+    const uint8_t* has_point;
+    const uint32_t* fv_nodes;
+    const int32_t* fv_start;        /* n_fv + 1 */
+    const int32_t* fv_features;
+    int32_t n, n_fv;
+    float Tcw[12], Ow[3];
+    int32_t pad;
+} spslam_tri_keyframe;
+
+/* Drop-in for ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs,
+ * bOnlyStereo): matched_pairs receives (idx1, idx2) in idx1 order (room for
+ * kf1->n pairs); returns nmatches, or a negative SPSLAM_ERR_*. */
+int spslam_search_for_triangulation(spslam_ctx* ctx, const spslam_tri_keyframe* kf1, const spslam_tri_keyframe* kf2,
+                                    const float* F12, int32_t* matched_pairs, int only_stereo,
+                                    int check_orientation);
+
+/* :298-443 for n_matches pairs (idx1 distinct): results[k] is pair k's record;
+ * *n_new the number of SPSLAM_TRI_NEW.  Nothing is marked. */
+int spslam_triangulate(spslam_ctx* ctx, const spslam_tri_keyframe* kf1, const spslam_tri_keyframe* kf2,
+                       const int32_t* matched_pairs, int n_matches, spslam_tri_result* results, int* n_new);
+
 /* ---------------------------------------------------------------- input images
  * Tracking::GrabImageRGBD's image preparation (src/Tracking.cc:208-229), the
  * first kernel of a step:

@@ -22,11 +22,14 @@
 //                       64 lanes split the node's frame features, reducing (best, first
 //                       index, second best) exactly as the sequential `<` scan; rotation
 //                       histogram + ComputeThreeMaxima at the end.
+//   triangulation_search_kernel  ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:657-823), described at
+//                       the kernel.
 // Integer / index work and fp64 sums in the reference's order: bit-exact.
 #include <hip/hip_runtime.h>
 
 #include "bow_launch.h"
 #include "orb_match_device.h"
+#include "triangulate_launch.h"
 
 namespace spslam {
 namespace bow {
@@ -225,6 +228,17 @@ __device__ __forceinline__ Best merge(const Best& a, const Best& b) {
     return r;
 }
 
+// position of node `id` in the ascending node list of a FeatureVector, -1 when absent: the shared-node
+// intersection of SearchByBoW / SearchForTriangulation (the reference's lower_bound walk)
+__device__ __forceinline__ int find_node(const uint32_t* __restrict__ nodes, int n, uint32_t id) {
+    int l = 0, h = n;
+    while (l < h) {
+        const int mid = (l + h) >> 1;
+        if (nodes[mid] < id) l = mid + 1; else h = mid;
+    }
+    return l < n && nodes[l] == id ? l : -1;
+}
+
 __global__ __launch_bounds__(kThreads) void bow_search_kernel(const int2* __restrict__ pairs, BowSide K, BowSide F,
                                                               float nn_ratio, int check_ori,
                                                               int32_t* __restrict__ match_out,
@@ -252,13 +266,8 @@ __global__ __launch_bounds__(kThreads) void bow_search_kernel(const int2* __rest
     const uint32_t* fn = F.fv_nodes + (size_t)fr * F.cap;
     const int nk = K.n_fv[kf], nfv = F.n_fv[fr];
     for (int a = t; a < nk; a += kThreads) {
-        const uint32_t id = kn[a];
-        int l = 0, h = nfv;
-        while (l < h) {
-            const int mid = (l + h) >> 1;
-            if (fn[mid] < id) l = mid + 1; else h = mid;
-        }
-        if (l < nfv && fn[l] == id) shared_nodes[atomicAdd(&n_shared, 1)] = make_int2(a, l);
+        const int l = find_node(fn, nfv, kn[a]);
+        if (l >= 0) shared_nodes[atomicAdd(&n_shared, 1)] = make_int2(a, l);
     }
     __syncthreads();
     const int32_t* ks = K.fv_start + (size_t)kf * (K.cap + 1);
@@ -325,7 +334,168 @@ __global__ __launch_bounds__(kThreads) void bow_search_kernel(const int2* __rest
     if (t == 0) nmatches_out[p] = n_total - n_removed;
 }
 
+// ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:657-823, CheckDistEpipolarLine :140-157), workgroup per
+// (current keyframe, neighbour) pair.  vbMatched2 is never written in the reference, so every key-1 feature without
+// a map point is an independent item: the items of the shared nodes are listed in LDS (any order), and a group of
+// kTriGroup lanes scans the item's key-2 node list, each lane keeping (distance, list position) of its own
+// candidates that pass the has-point, stereo, TH_LOW, epipole and epipolar-line tests.  The reference keeps the
+// smallest distance and, on a tie, the later position (`dist > bestDist` lets an equal one through): the minimum
+// of (distance << 16 | 0xFFFF - position).  Rotation histogram + ComputeThreeMaxima at the end.
+__global__ __launch_bounds__(kThreads) void triangulation_search_kernel(
+    const spslam_tri_pair* __restrict__ pairs, spslam_tri_side S, TriConsts C, int only_stereo, int check_ori,
+    int check_baseline, int32_t* __restrict__ match_out, int* __restrict__ nmatches_out,
+    uint8_t* __restrict__ pair_status) {
+    extern __shared__ int smem[];
+    int2* items = reinterpret_cast<int2*>(smem);                          // [cap] (idx1, key-2 node position)
+    signed char* bin = reinterpret_cast<signed char*>(items + S.cap);     // [cap]
+    __shared__ int hist[kHisto];
+    __shared__ int n_items, n_total, n_removed;
+    __shared__ int ind[3];
+    const int p = blockIdx.x, t = threadIdx.x;
+    const spslam_tri_pair* P = pairs + p;
+    const int k1 = P->kf1, k2 = P->kf2, cap = S.cap;
+    const int n1 = min(S.counts[k1], cap), n2 = min(S.counts[k2], cap);
+    int32_t* mo = match_out + P->out_offset;
+    int status = SPSLAM_TRI_PAIR_SEARCHED;
+    if (P->flags & SPSLAM_TRI_PAIR_SKIP) {
+        status = SPSLAM_TRI_PAIR_SKIPPED;
+    } else if (check_baseline) {  // LocalMapping.cc:258-264: vBaseline = Ow2 - Ow1, baseline < pKF2->mb
+        const float baseline = (float)tri::norm3(__fsub_rn(P->Ow2[0], P->Ow1[0]), __fsub_rn(P->Ow2[1], P->Ow1[1]),
+                                                 __fsub_rn(P->Ow2[2], P->Ow1[2]));
+        if (baseline < C.mb) status = SPSLAM_TRI_PAIR_SHORT_BASELINE;
+    }
+    for (int i = t; i < n1; i += kThreads) mo[i] = -1;
+    for (int i = t; i < cap; i += kThreads) bin[i] = -1;
+    if (t < kHisto) hist[t] = 0;
+    if (t == 0) {
+        n_items = 0; n_total = 0; n_removed = 0;
+        if (pair_status) pair_status[p] = (uint8_t)status;
+    }
+    if (status != SPSLAM_TRI_PAIR_SEARCHED) {  // uniform over the workgroup
+        if (t == 0) nmatches_out[p] = 0;
+        return;
+    }
+    __syncthreads();
+    const uint32_t* nodes1 = S.fv_nodes + (size_t)k1 * cap;
+    const uint32_t* nodes2 = S.fv_nodes + (size_t)k2 * cap;
+    const int32_t* fs1 = S.fv_start + (size_t)k1 * (cap + 1);
+    const int32_t* fs2 = S.fv_start + (size_t)k2 * (cap + 1);
+    const int32_t* feat1 = S.fv_features + (size_t)k1 * cap;
+    const int32_t* feat2 = S.fv_features + (size_t)k2 * cap;
+    const uint8_t* has1 = S.has_point + (size_t)k1 * cap;
+    const uint8_t* has2 = S.has_point + (size_t)k2 * cap;
+    const float* ur1 = S.uright + (size_t)k1 * cap;
+    const float* ur2 = S.uright + (size_t)k2 * cap;
+    const spslam_keypoint* kun1 = S.keys_un + (size_t)k1 * cap;
+    const spslam_keypoint* kun2 = S.keys_un + (size_t)k2 * cap;
+    const uint4* desc1 = reinterpret_cast<const uint4*>(S.desc + (size_t)k1 * cap * 32);
+    const uint4* desc2 = reinterpret_cast<const uint4*>(S.desc + (size_t)k2 * cap * 32);
+    const int nfv1 = min(S.n_fv[k1], cap), nfv2 = min(S.n_fv[k2], cap);
+    for (int a = t; a < nfv1; a += kThreads) {
+        const int l = find_node(nodes2, nfv2, nodes1[a]);
+        if (l < 0) continue;
+        for (int q = fs1[a]; q < fs1[a + 1]; q++) {
+            const int idx1 = feat1[q];
+            if ((unsigned)idx1 >= (unsigned)n1 || has1[idx1]) continue;            // :699
+            if (only_stereo && !(ur1[idx1] >= 0.f)) continue;
+            const int slot = atomicAdd(&n_items, 1);
+            if (slot < cap) items[slot] = make_int2(idx1, l);
+        }
+    }
+    __syncthreads();
+    // the epipole in the second image (:664-670): C2 = R2w*Cw + t2w
+    const float* T2 = P->Tcw2;
+    const float c2x = tri::row3(T2[0], T2[1], T2[2], P->Ow1[0], P->Ow1[1], P->Ow1[2], T2[3]);
+    const float c2y = tri::row3(T2[4], T2[5], T2[6], P->Ow1[0], P->Ow1[1], P->Ow1[2], T2[7]);
+    const float c2z = tri::row3(T2[8], T2[9], T2[10], P->Ow1[0], P->Ow1[1], P->Ow1[2], T2[11]);
+    const float invz = 1.0f / c2z;
+    const float ex = __fmaf_rn(__fmul_rn(C.fx, c2x), invz, C.cx);
+    const float ey = __fmaf_rn(__fmul_rn(C.fy, c2y), invz, C.cy);
+    const float* F = P->F12;
+    const int g = t & (kTriGroup - 1);
+    const int total = min(n_items, cap);
+    int count = 0;
+    for (int it = t / kTriGroup; it < total; it += kThreads / kTriGroup) {
+        const int2 item = items[it];
+        const int idx1 = item.x;
+        const float x1 = kun1[idx1].x, y1 = kun1[idx1].y;
+        // CheckDistEpipolarLine's l = x1'F12 = [a b c]
+        const float la = __fadd_rn(__fmaf_rn(x1, F[0], __fmul_rn(y1, F[3])), F[6]);
+        const float lb = __fadd_rn(__fmaf_rn(x1, F[1], __fmul_rn(y1, F[4])), F[7]);
+        const float lc = __fadd_rn(__fmaf_rn(x1, F[2], __fmul_rn(y1, F[5])), F[8]);
+        const float den = __fmaf_rn(la, la, __fmul_rn(lb, lb));
+        const bool stereo1 = ur1[idx1] >= 0.f;
+        const uint4 a0 = desc1[2 * idx1], a1 = desc1[2 * idx1 + 1];
+        const int f0 = fs2[item.y], f1 = fs2[item.y + 1];
+        int key = 0x7fffffff;
+        for (int r = f0 + g; r < f1; r += kTriGroup) {
+            const int idx2 = feat2[r];
+            if ((unsigned)idx2 >= (unsigned)n2 || has2[idx2]) continue;            // :722
+            const bool stereo2 = ur2[idx2] >= 0.f;
+            if (only_stereo && !stereo2) continue;
+            const int d = hamming(a0, a1, desc2[2 * idx2], desc2[2 * idx2 + 1]);
+            const int cand = (d << 16) | (0xFFFF - (r - f0));
+            if (d > kThLow || cand > key) continue;                                 // :736
+            const float x2 = kun2[idx2].x, y2 = kun2[idx2].y;
+            const int oct = kun2[idx2].octave;
+            if (!stereo1 && !stereo2) {                                             // :741
+                const float dx = __fsub_rn(ex, x2), dy = __fsub_rn(ey, y2);
+                if (__fmaf_rn(dx, dx, __fmul_rn(dy, dy)) < __fmul_rn(100.f, level_entry(C.scale, oct))) continue;
+            }
+            const float num = __fadd_rn(__fmaf_rn(la, x2, __fmul_rn(lb, y2)), lc);
+            if (den == 0.f) continue;
+            const float dsqr = __fmul_rn(num, num) / den;
+            if (!((double)dsqr < 3.84 * (double)level_entry(C.sigma2, oct))) continue;
+            key = cand;
+        }
+#pragma unroll
+        for (int o = 1; o < kTriGroup; o <<= 1) key = min(key, __shfl_xor(key, o));
+        if (g == 0 && key != 0x7fffffff) {
+            const int idx2 = feat2[f0 + (0xFFFF - (key & 0xFFFF))];
+            mo[idx1] = idx2;
+            if (check_ori) {
+                const int bn = rotation_bin(kun1[idx1].angle, kun2[idx2].angle);
+                if ((unsigned)bn < (unsigned)kHisto) {  // the reference asserts it
+                    bin[idx1] = (signed char)bn;
+                    atomicAdd(&hist[bn], 1);
+                }
+            }
+            count++;
+        }
+    }
+    if (count) atomicAdd(&n_total, count);
+    __syncthreads();
+    if (check_ori) {
+        if (t == 0) three_maxima(hist, &ind[0], &ind[1], &ind[2]);
+        __syncthreads();
+        int removed = 0;
+        for (int i = t; i < n1; i += kThreads) {
+            const int bn = bin[i];
+            if (bn >= 0 && bn != ind[0] && bn != ind[1] && bn != ind[2]) {
+                mo[i] = -1;
+                removed++;
+            }
+        }
+        if (removed) atomicAdd(&n_removed, removed);
+        __syncthreads();
+    }
+    if (t == 0) nmatches_out[p] = n_total - n_removed;
+}
+
 }  // namespace bow
+
+hipError_t triangulation_search_launch(int n_pairs, const spslam_tri_pair* pairs, const spslam_tri_side& side,
+                                       const TriConsts& C, int only_stereo, int check_ori, int check_baseline,
+                                       int32_t* match12, int* nmatches, uint8_t* pair_status, hipStream_t s) {
+    if (n_pairs < 1 || side.cap < 1 || side.cap > 8192) return hipErrorInvalidValue;
+    const size_t lds = ((size_t)side.cap * 9 + 15) / 16 * 16;  // <= 72 KB
+    static const hipError_t lds_attr = hipFuncSetAttribute((const void*)bow::triangulation_search_kernel,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 9);
+    if (lds_attr != hipSuccess) return lds_attr;
+    hipLaunchKernelGGL(bow::triangulation_search_kernel, dim3(n_pairs), dim3(bow::kThreads), lds, s, pairs, side, C,
+                       only_stereo, check_ori, check_baseline, match12, nmatches, pair_status);
+    return hipGetLastError();
+}
 
 hipError_t bow_transform_launch(const VocabDev& V, int n_frames, const uint8_t* desc, const int* counts, int cap,
                                 int levelsup, uint32_t* s_word, double* s_weight, uint32_t* s_node,

@@ -56,4 +56,24 @@ struct BowSide {
 hipError_t bow_search_launch(int n_pairs, const int2* pairs, const BowSide& kf, const BowSide& fr, float nn_ratio,
                              int check_ori, int32_t* match, int* nmatches, hipStream_t s, KernelTimer* timer);
 
+// Camera and level tables of the CreateNewMapPoints kernels (Frame.cc:118-124: invfx = 1.0f/fx, mb = mbf/fx;
+// ratio_factor = 1.5f*mfScaleFactor, LocalMapping.cc:245).
+struct TriConsts {
+    float fx, fy, cx, cy, invfx, invfy, bf, mb, ratio_factor;
+    float scale[8], sigma2[8];  // mvScaleFactors, mvLevelSigma2
+};
+
+// lanes that scan one key-1 feature's node list (triangulation_search_kernel); a power of two up to 64.
+// -DSPSLAM_TRI_GROUP=<n> builds a measurement variant (tools/create_points_bench.py).
+#ifndef SPSLAM_TRI_GROUP
+#define SPSLAM_TRI_GROUP 8
+#endif
+constexpr int kTriGroup = SPSLAM_TRI_GROUP;
+
+// ORBmatcher::SearchForTriangulation per pair.  check_baseline: LocalMapping.cc:258-264 first (a short pair gives
+// no match).  pair_status may be NULL.
+hipError_t triangulation_search_launch(int n_pairs, const spslam_tri_pair* pairs, const spslam_tri_side& side,
+                                       const TriConsts& C, int only_stereo, int check_ori, int check_baseline,
+                                       int32_t* match12, int* nmatches, uint8_t* pair_status, hipStream_t s);
+
 }  // namespace spslam

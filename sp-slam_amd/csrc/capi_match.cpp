@@ -1,10 +1,12 @@
 // C ABI (include/spslam_gpu.h): projection, local-point and Fuse search, the map-point refresh, the tracking graph,
 // masked copies and bag of words.
 #include "capi_ctx.h"
+#include "triangulate_launch.h"
 
 #include <cmath>
 #include <cstring>
 #include <sstream>
+#include <vector>
 
 namespace {
 
@@ -727,6 +729,211 @@ int spslam_search_by_bow(spslam_ctx* c, const uint8_t* kf_desc, const spslam_key
     if (f_n) HIP_CHECK(c, hipMemcpyAsync(match, st.slot<int32_t>(16), fn * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(c, hipMemcpyAsync(nmatches, st.slot<int>(17), 4, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- CreateNewMapPoints
+namespace {
+
+// Frame.cc:118-124 (invfx = 1.0f/fx, mb = mbf/fx), LocalMapping.cc:245 (ratioFactor = 1.5f*mfScaleFactor)
+TriConsts tri_consts(const spslam_ctx* c) {
+    TriConsts C{};
+    C.fx = c->fg.fx; C.fy = c->fg.fy; C.cx = c->fg.cx; C.cy = c->fg.cy; C.bf = c->fg.bf;
+    C.invfx = 1.0f / C.fx;
+    C.invfy = 1.0f / C.fy;
+    C.mb = C.bf / C.fx;
+    C.ratio_factor = 1.5f * (float)c->p.scale_factor;
+    for (int l = 0; l < 8; l++) {
+        C.scale[l] = l < c->p.nlevels ? c->scale[l] : 0.f;
+        C.sigma2[l] = l < c->p.nlevels ? c->sigma2[l] : 0.f;
+    }
+    return C;
+}
+
+bool tri_side_ok(const spslam_tri_side* s) {
+    return s && s->keys && s->keys_un && s->uright && s->depth && s->desc && s->has_point && s->counts &&
+           s->fv_nodes && s->fv_start && s->fv_features && s->n_fv && s->cap >= 1 && s->cap <= 8192;
+}
+
+bool tri_keyframe_ok(const spslam_tri_keyframe* k) {
+    if (!k || k->n < 0 || k->n > 8192 || k->n_fv < 0 || k->n_fv > std::max(k->n, 1) || !k->fv_start) return false;
+    if (k->n && (!k->keys || !k->keys_un || !k->uright || !k->depth || !k->desc || !k->has_point)) return false;
+    if (k->n_fv && (!k->fv_nodes || !k->fv_features)) return false;
+    const int m = k->fv_start[k->n_fv];
+    return k->fv_start[0] == 0 && m >= 0 && m <= k->n;
+}
+
+// The two keyframes of a drop-in call as slots 0 and 1 of a batch of cap keypoints, with one pair record.
+struct TriStage {
+    Stage st;
+    spslam_tri_side side{};
+    int cap = 1;
+    explicit TriStage(spslam_ctx* c) : st(c) {}
+    // slots: 0 pair, 1..10 the side's arrays, 11 match12, 12 results, 13 {nmatches, n_new}
+    int open(spslam_ctx* c, const spslam_tri_keyframe* k[2], const float* F12, const int32_t* match12) {
+        cap = std::max(std::max(k[0]->n, k[1]->n), 1);
+        const size_t C = (size_t)cap, kKp = sizeof(spslam_keypoint);
+        std::vector<uint8_t> h[10];
+        const size_t unit[10] = {kKp, kKp, 4, 4, 32, 1, 4, 4, 4, 4};
+        const size_t per_slot[10] = {C, C, C, C, C, C, 1, C, C + 1, C};
+        for (int a = 0; a < 10; a++) h[a].assign(2 * per_slot[a] * unit[a], 0);
+        for (int s = 0; s < 2; s++) {
+            const spslam_tri_keyframe& q = *k[s];
+            const size_t n = (size_t)q.n, nf = (size_t)q.n_fv, m = (size_t)q.fv_start[q.n_fv];
+            const void* src[10] = {q.keys, q.keys_un, q.uright, q.depth, q.desc, q.has_point, &q.n, q.fv_nodes,
+                                   q.fv_start, q.fv_features};
+            const size_t cnt[10] = {n, n, n, n, n, n, 1, nf, nf + 1, m};
+            for (int a = 0; a < 10; a++)
+                if (cnt[a]) std::memcpy(h[a].data() + s * per_slot[a] * unit[a], src[a], cnt[a] * unit[a]);
+        }
+        const int32_t nfv[2] = {k[0]->n_fv, k[1]->n_fv};
+        spslam_tri_pair P{};
+        P.kf1 = 0; P.kf2 = 1;
+        std::memcpy(P.Tcw1, k[0]->Tcw, sizeof P.Tcw1);
+        std::memcpy(P.Tcw2, k[1]->Tcw, sizeof P.Tcw2);
+        std::memcpy(P.Ow1, k[0]->Ow, sizeof P.Ow1);
+        std::memcpy(P.Ow2, k[1]->Ow, sizeof P.Ow2);
+        if (F12) std::memcpy(P.F12, F12, sizeof P.F12);
+        if (int rc = st.open({{&P, sizeof P}, {h[0].data(), h[0].size()}, {h[1].data(), h[1].size()},
+                              {h[2].data(), h[2].size()}, {h[3].data(), h[3].size()}, {h[4].data(), h[4].size()},
+                              {h[5].data(), h[5].size()}, {h[6].data(), h[6].size()}, {h[7].data(), h[7].size()},
+                              {h[8].data(), h[8].size()}, {h[9].data(), h[9].size()},
+                              {match12, match12 ? C * 4 : 0, C * 4}, C * sizeof(spslam_tri_result), 8,
+                              {nfv, sizeof nfv}}))
+            return rc;
+        // the uploads read the vectors above: they must be done before those go out of scope
+        HIP_CHECK(c, hipStreamSynchronize(c->stream));
+        side.keys = st.slot<spslam_keypoint>(1);
+        side.keys_un = st.slot<spslam_keypoint>(2);
+        side.uright = st.slot<float>(3);
+        side.depth = st.slot<float>(4);
+        side.desc = st.slot<uint8_t>(5);
+        side.has_point = st.slot<uint8_t>(6);
+        side.counts = st.slot<int>(7);
+        side.fv_nodes = st.slot<uint32_t>(8);
+        side.fv_start = st.slot<int32_t>(9);
+        side.fv_features = st.slot<int32_t>(10);
+        side.n_fv = st.slot<int>(14);
+        side.cap = cap;
+        return SPSLAM_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int spslam_search_for_triangulation_batch_device(spslam_ctx* c, int n_pairs, const spslam_tri_pair* d_pairs,
+                                                 const spslam_tri_side* side, int only_stereo,
+                                                 int check_orientation, int32_t* d_match12, int* d_nmatches,
+                                                 void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_pairs < 1 || !d_pairs || !tri_side_ok(side) || !d_match12 || !d_nmatches)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_search_for_triangulation_batch_device");
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, triangulation_search_launch(n_pairs, d_pairs, *side, tri_consts(c), only_stereo != 0,
+                                             check_orientation != 0, 0, d_match12, d_nmatches, nullptr,
+                                             (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_triangulate_batch_device(spslam_ctx* c, int n_pairs, const spslam_tri_pair* d_pairs,
+                                    const spslam_tri_side* side, const int32_t* d_match12, int mark,
+                                    spslam_tri_result* d_results, int* d_n_new, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_pairs < 1 || !d_pairs || !tri_side_ok(side) || !d_match12 || !d_results || !d_n_new)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_triangulate_batch_device");
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, triangulate_launch(n_pairs, d_pairs, *side, tri_consts(c), d_match12, mark != 0, d_results, d_n_new,
+                                    (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_create_new_points_batch_device(spslam_ctx* c, int n_pairs, const spslam_tri_pair* d_pairs,
+                                          const spslam_tri_side* side, int32_t* d_match12, int* d_nmatches,
+                                          spslam_tri_result* d_results, int* d_n_new, uint8_t* d_pair_status,
+                                          void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_pairs < 1 || !d_pairs || !tri_side_ok(side) || !d_match12 || !d_nmatches || !d_results || !d_n_new ||
+        !d_pair_status)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_create_new_points_batch_device");
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const TriConsts C = tri_consts(c);
+    hipStream_t s = (hipStream_t)hip_stream;
+    // matcher(0.6, false).SearchForTriangulation(..., bOnlyStereo = false) (LocalMapping.cc:228, :283)
+    HIP_CHECK(c, triangulation_search_launch(n_pairs, d_pairs, *side, C, 0, 0, 1, d_match12, d_nmatches,
+                                             d_pair_status, s));
+    HIP_CHECK(c, triangulate_launch(n_pairs, d_pairs, *side, C, d_match12, 1, d_results, d_n_new, s));
+    return SPSLAM_OK;
+}
+
+int spslam_search_for_triangulation(spslam_ctx* c, const spslam_tri_keyframe* kf1, const spslam_tri_keyframe* kf2,
+                                    const float* F12, int32_t* matched_pairs, int only_stereo,
+                                    int check_orientation) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!tri_keyframe_ok(kf1) || !tri_keyframe_ok(kf2) || !F12 || (kf1->n && !matched_pairs))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_search_for_triangulation");
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    TriStage ts(c);
+    const spslam_tri_keyframe* k[2] = {kf1, kf2};
+    if (int rc = ts.open(c, k, F12, nullptr)) return rc;
+    int rc = spslam_search_for_triangulation_batch_device(c, 1, ts.st.slot<spslam_tri_pair>(0), &ts.side, only_stereo,
+                                                          check_orientation, ts.st.slot<int32_t>(11),
+                                                          ts.st.slot<int>(13), c->stream);
+    if (rc) return rc;
+    std::vector<int32_t> match((size_t)ts.cap);
+    int nmatches = 0;
+    HIP_CHECK(c, hipMemcpyAsync(match.data(), ts.st.slot<int32_t>(11), match.size() * 4, hipMemcpyDeviceToHost,
+                                c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(&nmatches, ts.st.slot<int>(13), 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = ts.st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    int n = 0;
+    for (int i = 0; i < kf1->n; i++)  // vMatchedPairs: idx1 order (:811-816)
+        if (match[i] >= 0) {
+            matched_pairs[2 * n] = i;
+            matched_pairs[2 * n + 1] = match[i];
+            n++;
+        }
+    if (n != nmatches) return fail(c, SPSLAM_ERR_HIP, "spslam_search_for_triangulation: count mismatch%s", "");
+    return nmatches;
+}
+
+int spslam_triangulate(spslam_ctx* c, const spslam_tri_keyframe* kf1, const spslam_tri_keyframe* kf2,
+                       const int32_t* matched_pairs, int n_matches, spslam_tri_result* results, int* n_new) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!tri_keyframe_ok(kf1) || !tri_keyframe_ok(kf2) || n_matches < 0 || !n_new ||
+        (n_matches && (!matched_pairs || !results)))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_triangulate");
+    const int cap = std::max(std::max(kf1->n, kf2->n), 1);
+    std::vector<int32_t> match((size_t)cap, -1);
+    for (int k = 0; k < n_matches; k++) {
+        const int i1 = matched_pairs[2 * k], i2 = matched_pairs[2 * k + 1];
+        if (i1 < 0 || i1 >= kf1->n || i2 < 0 || i2 >= kf2->n || match[i1] >= 0)
+            return fail(c, SPSLAM_ERR_ARG, "spslam_triangulate: a pair outside the keyframes or idx1 twice%s", "");
+        match[i1] = i2;
+    }
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    TriStage ts(c);
+    const spslam_tri_keyframe* k[2] = {kf1, kf2};
+    if (int rc = ts.open(c, k, nullptr, match.data())) return rc;
+    int rc = spslam_triangulate_batch_device(c, 1, ts.st.slot<spslam_tri_pair>(0), &ts.side, ts.st.slot<int32_t>(11), 0,
+                                             ts.st.slot<spslam_tri_result>(12), ts.st.slot<int>(13) + 1, c->stream);
+    if (rc) return rc;
+    std::vector<spslam_tri_result> rec((size_t)cap);
+    HIP_CHECK(c, hipMemcpyAsync(rec.data(), ts.st.slot<void>(12), rec.size() * sizeof(spslam_tri_result),
+                                hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(n_new, ts.st.slot<int>(13) + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = ts.st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    for (int q = 0; q < n_matches; q++) results[q] = rec[matched_pairs[2 * q]];
     return SPSLAM_OK;
 }
 

@@ -232,3 +232,133 @@ class PointRefresh:
         self.ex._check(self.ex.lib.spslam_map_points_refresh_batch_device(
             self.ex.ctx, ctypes.byref(refresh_map), d_rows, n, what, d_keys_un or None, d_desc or None, cap, d_status,
             stream or None))
+
+
+# ---------------------------------------------------------------- LocalMapping: CreateNewMapPoints
+TRI_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("Tcw1", "<f4", 12), ("Tcw2", "<f4", 12), ("Ow1", "<f4", 3),
+                           ("Ow2", "<f4", 3), ("F12", "<f4", 9), ("out_offset", "<i4"), ("flags", "<i4")])
+assert TRI_PAIR_DTYPE.itemsize == 172
+TRI_RESULT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("idx2", "<i4"), ("status", "u1"),
+                             ("source", "u1"), ("pad", "<u2")])
+assert TRI_RESULT_DTYPE.itemsize == 20
+TRI_NEW, TRI_NO_MATCH, TRI_LOW_PARALLAX, TRI_W_ZERO, TRI_BEHIND_1, TRI_BEHIND_2, TRI_REPROJ_1, TRI_REPROJ_2, \
+    TRI_ZERO_DIST, TRI_SCALE = range(10)
+TRI_FROM_SVD, TRI_FROM_STEREO_1, TRI_FROM_STEREO_2 = range(3)
+TRI_PAIR_SEARCHED, TRI_PAIR_SKIPPED, TRI_PAIR_SHORT_BASELINE = range(3)
+TRI_PAIR_SKIP = 1
+TRI_MAX_CAP = 8192
+# the arrays of spslam_tri_side before `cap`, in its order
+TRI_SIDE_ARRAYS = ("keys", "keys_un", "uright", "depth", "desc", "has_point", "counts", "fv_nodes", "fv_start",
+                   "fv_features", "n_fv")
+
+
+class TriSide(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in TRI_SIDE_ARRAYS] + [("cap", ctypes.c_int32),
+                                                                         ("pad", ctypes.c_int32)]
+
+
+class TriKeyframe(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in ("keys", "keys_un", "uright", "depth", "desc", "has_point",
+                                                     "fv_nodes", "fv_start", "fv_features")] + \
+               [("n", ctypes.c_int32), ("n_fv", ctypes.c_int32), ("Tcw", ctypes.c_float * 12),
+                ("Ow", ctypes.c_float * 3), ("pad", ctypes.c_int32)]
+
+
+spslam_gpu.EXPORTED += ["spslam_search_for_triangulation", "spslam_search_for_triangulation_batch_device",
+                        "spslam_triangulate", "spslam_triangulate_batch_device",
+                        "spslam_create_new_points_batch_device"]
+
+
+def _bind_tri(lib):
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.spslam_search_for_triangulation.argtypes = [vp, vp, vp, vp, vp, ci, ci]
+    lib.spslam_search_for_triangulation_batch_device.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, vp]
+    lib.spslam_triangulate.argtypes = [vp, vp, vp, vp, ci, vp, vp]
+    lib.spslam_triangulate_batch_device.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp]
+    lib.spslam_create_new_points_batch_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+
+
+class _TriHost:
+    """A keyframe dict (keys, kun, ur, depth, desc, has, fv = dict(nodes, start, features), Tcw [3x4 or 4x4], Ow)
+    as a spslam_tri_keyframe; holds the arrays alive."""
+
+    def __init__(self, kf):
+        n = len(kf["kun"])
+        self.a = [np.ascontiguousarray(kf["keys"], spslam_gpu.KEYPOINT_DTYPE),
+                  np.ascontiguousarray(kf["kun"], spslam_gpu.KEYPOINT_DTYPE),
+                  np.ascontiguousarray(kf["ur"], np.float32), np.ascontiguousarray(kf["depth"], np.float32),
+                  np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32),
+                  np.ascontiguousarray(kf["has"], np.uint8),
+                  np.ascontiguousarray(kf["fv"]["nodes"], np.uint32),
+                  np.ascontiguousarray(kf["fv"]["start"], np.int32),
+                  np.ascontiguousarray(kf["fv"]["features"], np.int32)]
+        ptr = lambda x: x.ctypes.data if x.size else None  # noqa: E731
+        T = np.asarray(kf["Tcw"], np.float32).reshape(-1, 4)[:3].reshape(12)
+        self.rec = TriKeyframe(*[ptr(x) for x in self.a], n, len(self.a[6]), (ctypes.c_float * 12)(*T.tolist()),
+                               (ctypes.c_float * 3)(*np.asarray(kf["Ow"], np.float32).tolist()), 0)
+
+
+class SearchForTriangulation:
+    """GPU ORBmatcher::SearchForTriangulation on a context configured with spslam_frame_configure."""
+
+    def __init__(self, ex: spslam_gpu.OrbExtractor):
+        self.ex = ex
+        _bind_tri(ex.lib)
+
+    def __call__(self, kf1, kf2, F12, only_stereo=False, check_orientation=False):
+        """Returns (vMatchedPairs [nmatches, 2] in idx1 order, nmatches)."""
+        a, b = _TriHost(kf1), _TriHost(kf2)
+        F = np.ascontiguousarray(F12, np.float32).reshape(9)
+        pairs = np.zeros((max(a.rec.n, 1), 2), np.int32)
+        rc = self.ex.lib.spslam_search_for_triangulation(self.ex.ctx, ctypes.byref(a.rec), ctypes.byref(b.rec),
+                                                         F.ctypes.data, pairs.ctypes.data, int(only_stereo),
+                                                         int(check_orientation))
+        if rc < 0:
+            self.ex._check(rc)
+        return pairs[:rc], rc
+
+    def batch_device(self, n_pairs, d_pairs, side: TriSide, only_stereo, check_orientation, d_match12, d_nmatches,
+                     stream=0):
+        self.ex._check(self.ex.lib.spslam_search_for_triangulation_batch_device(
+            self.ex.ctx, n_pairs, d_pairs, ctypes.byref(side), int(only_stereo), int(check_orientation), d_match12,
+            d_nmatches, stream or None))
+
+
+class Triangulate:
+    """GPU triangulation and checks of LocalMapping::CreateNewMapPoints (:298-443) per matched pair."""
+
+    def __init__(self, ex: spslam_gpu.OrbExtractor):
+        self.ex = ex
+        _bind_tri(ex.lib)
+
+    def __call__(self, kf1, kf2, matched_pairs):
+        """Returns (one TRI_RESULT_DTYPE record per pair, n_new)."""
+        a, b = _TriHost(kf1), _TriHost(kf2)
+        mp = np.ascontiguousarray(matched_pairs, np.int32).reshape(-1, 2)
+        res = np.zeros(max(len(mp), 1), TRI_RESULT_DTYPE)
+        n_new = ctypes.c_int(0)
+        self.ex._check(self.ex.lib.spslam_triangulate(self.ex.ctx, ctypes.byref(a.rec), ctypes.byref(b.rec),
+                                                      mp.ctypes.data if len(mp) else None, len(mp),
+                                                      res.ctypes.data, ctypes.byref(n_new)))
+        return res[:len(mp)], n_new.value
+
+    def batch_device(self, n_pairs, d_pairs, side: TriSide, d_match12, mark, d_results, d_n_new, stream=0):
+        self.ex._check(self.ex.lib.spslam_triangulate_batch_device(
+            self.ex.ctx, n_pairs, d_pairs, ctypes.byref(side), d_match12, int(mark), d_results, d_n_new,
+            stream or None))
+
+
+class CreateNewPoints:
+    """One neighbour round of LocalMapping::CreateNewMapPoints for a batch of sequences: baseline test, search,
+    triangulation, has-point marks.  The pairs of one call must not share a keyframe slot; calls on one stream are
+    ordered.  The map mutation stays with the caller."""
+
+    def __init__(self, ex: spslam_gpu.OrbExtractor):
+        self.ex = ex
+        _bind_tri(ex.lib)
+
+    def batch_device(self, n_pairs, d_pairs, side: TriSide, d_match12, d_nmatches, d_results, d_n_new,
+                     d_pair_status, stream=0):
+        self.ex._check(self.ex.lib.spslam_create_new_points_batch_device(
+            self.ex.ctx, n_pairs, d_pairs, ctypes.byref(side), d_match12, d_nmatches, d_results, d_n_new,
+            d_pair_status, stream or None))
