@@ -239,6 +239,26 @@ __device__ __forceinline__ int find_node(const uint32_t* __restrict__ nodes, int
     return l < n && nodes[l] == id ? l : -1;
 }
 
+// The rotation-consistency tail of SearchByBoW and SearchForTriangulation: ComputeThreeMaxima over the histogram,
+// then every match among the first n whose bin is none of the three is cleared and counted in *n_removed.  The
+// whole workgroup calls it after the barrier that completes hist and bin; it ends with a barrier.
+__device__ __forceinline__ void keep_three_maxima(const int* hist, int* ind, const signed char* bin, int32_t* match,
+                                                  int n, int* n_removed) {
+    const int t = threadIdx.x;
+    if (t == 0) three_maxima(hist, &ind[0], &ind[1], &ind[2]);
+    __syncthreads();
+    int removed = 0;
+    for (int i = t; i < n; i += kThreads) {
+        const int bn = bin[i];
+        if (bn >= 0 && bn != ind[0] && bn != ind[1] && bn != ind[2]) {
+            match[i] = -1;
+            removed++;
+        }
+    }
+    if (removed) atomicAdd(n_removed, removed);
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(kThreads) void bow_search_kernel(const int2* __restrict__ pairs, BowSide K, BowSide F,
                                                               float nn_ratio, int check_ori,
                                                               int32_t* __restrict__ match_out,
@@ -315,20 +335,7 @@ __global__ __launch_bounds__(kThreads) void bow_search_kernel(const int2* __rest
     }
     if (lane == 0 && count) atomicAdd(&n_total, count);
     __syncthreads();
-    if (check_ori) {
-        if (t == 0) three_maxima(hist, &ind[0], &ind[1], &ind[2]);
-        __syncthreads();
-        int removed = 0;
-        for (int i = t; i < nF; i += kThreads) {
-            const int bn = bin[i];
-            if (bn >= 0 && bn != ind[0] && bn != ind[1] && bn != ind[2]) {
-                match[i] = -1;
-                removed++;
-            }
-        }
-        if (removed) atomicAdd(&n_removed, removed);
-        __syncthreads();
-    }
+    if (check_ori) keep_three_maxima(hist, ind, bin, match, nF, &n_removed);
     int32_t* mo = match_out + (size_t)p * F.cap;
     for (int i = t; i < nF; i += kThreads) mo[i] = match[i];
     if (t == 0) nmatches_out[p] = n_total - n_removed;
@@ -465,20 +472,7 @@ __global__ __launch_bounds__(kThreads) void triangulation_search_kernel(
     }
     if (count) atomicAdd(&n_total, count);
     __syncthreads();
-    if (check_ori) {
-        if (t == 0) three_maxima(hist, &ind[0], &ind[1], &ind[2]);
-        __syncthreads();
-        int removed = 0;
-        for (int i = t; i < n1; i += kThreads) {
-            const int bn = bin[i];
-            if (bn >= 0 && bn != ind[0] && bn != ind[1] && bn != ind[2]) {
-                mo[i] = -1;
-                removed++;
-            }
-        }
-        if (removed) atomicAdd(&n_removed, removed);
-        __syncthreads();
-    }
+    if (check_ori) keep_three_maxima(hist, ind, bin, mo, n1, &n_removed);
     if (t == 0) nmatches_out[p] = n_total - n_removed;
 }
 

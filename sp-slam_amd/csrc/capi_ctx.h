@@ -1,5 +1,6 @@
 // Private to the capi_*.cpp files: the context behind include/spslam_gpu.h, its device-buffer type, the error
-// helpers and the host-array staging of the drop-in entries.
+// helpers, the host-array staging of the drop-in entries, and the pieces the ORBmatcher entries share: the per-level
+// tables, the current frame of the window searches and the argument predicates of the batch forms.
 //
 // Nothing here falls back to a CPU path: if the HIP runtime or the gfx950 code object is unusable every entry
 // point returns SPSLAM_ERR_HIP.
@@ -27,6 +28,7 @@
 #include "map_point_launch.h"
 #include "track_launch.h"
 #include "grab_launch.h"
+#include "triangulate_launch.h"
 
 using namespace spslam;
 
@@ -256,9 +258,11 @@ struct Stage {
     Stage& operator=(const Stage&) = delete;
     ~Stage() { if (temporary && q) (void)hipFreeAsync(q, c->stream); }
     int open(std::initializer_list<StageSlot> slots, DevBuf<>* persistent = nullptr, size_t grow = 1) {
-        const int n = (int)slots.size();
+        return open(slots.begin(), (int)slots.size(), persistent, grow);
+    }
+    int open(const StageSlot* slots, int n, DevBuf<>* persistent = nullptr, size_t grow = 1) {
         if (n > kMaxSlots) return fail(c, SPSLAM_ERR_ARG, "too many staging slots%s", "");
-        const size_t bytes = stage_layout(slots.begin(), n, off);
+        const size_t bytes = stage_layout(slots, n, off);
         if (!persistent) {
             HIP_CHECK(c, hipMallocAsync((void**)&q, bytes, c->stream));
             temporary = true;
@@ -267,7 +271,7 @@ struct Stage {
             q = *persistent;
         }
         for (int i = 0; i < n; i++) {
-            const StageSlot& s = slots.begin()[i];
+            const StageSlot& s = slots[i];
             if (s.upload) HIP_CHECK(c, hipMemcpyAsync(q + off[i], s.src, s.upload, hipMemcpyHostToDevice, c->stream));
         }
         return SPSLAM_OK;
@@ -279,5 +283,66 @@ struct Stage {
         q = nullptr;
         if (t) HIP_CHECK(c, hipFreeAsync(t, c->stream));
         return SPSLAM_OK;
+    }
+};
+
+// An 8-entry per-level table of a kernel's constants from one of the context's ORBextractor vectors, zero past
+// nlevels.
+inline void level_table(const spslam_ctx* c, const std::vector<float>& v, float (&out)[8]) {
+    for (int l = 0; l < 8; l++) out[l] = l < c->p.nlevels ? v[l] : 0.f;
+}
+
+// camera, image bounds, grid and level scales of the configured frame stage
+inline MatchGeom match_geom(const spslam_ctx* c) {
+    MatchGeom g{};
+    g.fx = c->fg.fx; g.fy = c->fg.fy; g.cx = c->fg.cx; g.cy = c->fg.cy; g.bf = c->fg.bf;
+    g.min_x = c->fg.min_x; g.max_x = c->fg.max_x; g.min_y = c->fg.min_y; g.max_y = c->fg.max_y;
+    g.ginv_x = c->fg.ginv_x; g.ginv_y = c->fg.ginv_y;
+    level_table(c, c->scale, g.scale);
+    return g;
+}
+
+// The current frame's arrays of a window search's batch-device form (projection, local points, Fuse).
+inline bool match_current_ok(const MatchCurrent& m) {
+    return m.kun && m.desc && m.uright && m.grid_off && m.grid_idx && m.counts && m.cap >= 1 && m.cap <= (1 << 20);
+}
+
+// The spslam_track_batch fields every tracking entry reads; each entry adds what only it needs.
+inline bool track_batch_ok(const spslam_track_batch& b) {
+    return b.kp_counts && b.cap >= 1 && b.cap <= (1 << 20) && b.proj_frames && b.proj_points && b.proj_match &&
+           b.edge_of_kp;
+}
+
+// The current frame of a window search's host form: n_kp keypoints and their grid CSR.  open() stages it as slots
+// 0 .. 5 (keys_un, desc, uright, grid_off, grid_idx, count), every array padded to cap = max(n_kp, 1) entries, with
+// the entry's own slots behind them from kFirst on; current() is the device view of the opened stage.
+struct CurrentFrame {
+    static constexpr int kCells = SPSLAM_GRID_COLS * SPSLAM_GRID_ROWS, kFirst = 6;
+    const spslam_keypoint* keys_un;
+    const uint8_t* desc;
+    const float* uright;
+    int n_kp;
+    const int32_t* grid_off;
+    const int32_t* grid_idx;
+    int cap() const { return std::max(n_kp, 1); }
+    bool args_ok() const { return grid_off && n_kp >= 0 && (!n_kp || (keys_un && desc && uright && grid_idx)); }
+    // SPSLAM_OK, or the error of a grid CSR that does not fit the keypoints (call after args_ok)
+    int check_grid(spslam_ctx* c) const {
+        if (grid_off[0] != 0 || grid_off[kCells] > n_kp)
+            return fail(c, SPSLAM_ERR_ARG, "grid CSR does not fit the keypoints%s", "");
+        return SPSLAM_OK;
+    }
+    int open(Stage& st, std::initializer_list<StageSlot> entry_slots) const {
+        const size_t K = (size_t)n_kp, C = (size_t)cap();
+        std::vector<StageSlot> slots{{keys_un, K * sizeof(spslam_keypoint), C * sizeof(spslam_keypoint)},
+                                     {desc, K * 32, C * 32}, {uright, K * 4, C * 4},
+                                     {grid_off, (kCells + 1) * 4}, {grid_idx, (size_t)grid_off[kCells] * 4, C * 4},
+                                     {&n_kp, sizeof(int)}};
+        slots.insert(slots.end(), entry_slots.begin(), entry_slots.end());
+        return st.open(slots.data(), (int)slots.size());
+    }
+    MatchCurrent current(const Stage& st) const {
+        return {st.slot<spslam_keypoint>(0), st.slot<uint8_t>(1), st.slot<float>(2), st.slot<int32_t>(3),
+                st.slot<int32_t>(4), st.slot<int>(5), cap()};
     }
 };

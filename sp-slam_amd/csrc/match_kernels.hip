@@ -464,6 +464,14 @@ __global__ __launch_bounds__(64) void match_assign_kernel(const spslam_proj_fram
 #endif
 }
 
+// MapPoint::PredictScale: ceil(log(max_dist / dist) / mfLogScaleFactor), clamped to the levels; the correctly
+// rounded logf gives the same level as glibc's for every float ratio (tests/test_libm_restated.py)
+__device__ __forceinline__ int predict_scale(float max_dist, float dist, float log_scale_factor, int n_levels) {
+    const float ratio = __fdiv_rn(max_dist, dist);
+    const int n = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
+    return n < 0 ? 0 : (n >= n_levels ? n_levels - 1 : n);
+}
+
 // ---------------------------------------------------------------------------
 // Tracking::SearchLocalPoints: isInFrustum + PredictScale per local point,
 // then ORBmatcher::SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:
@@ -530,11 +538,7 @@ __global__ __launch_bounds__(kThreads) void local_window_kernel(const spslam_loc
         dot = __dadd_rn(dot, __dmul_rn((double)PO[2], (double)p.normal[2]));
         viewCos = (float)__ddiv_rn(dot, (double)dist);
         if (viewCos < P.view_cos_limit) break;
-        // PredictScale: ceil(log(ratio) / mfLogScaleFactor); the correctly rounded logf gives the same
-        // level as glibc's for every float ratio (tests/test_libm_restated.py)
-        const float ratio = __fdiv_rn(p.max_dist, dist);
-        int n = (int)ceilf(__fdiv_rn((float)log((double)ratio), P.log_scale_factor));
-        level = n < 0 ? 0 : (n >= P.n_levels ? P.n_levels - 1 : n);
+        level = predict_scale(p.max_dist, dist, P.log_scale_factor, P.n_levels);
         in = true;
     } while (false);
     if (in_view && sub == 0) in_view[F.point_offset + i] = in;
@@ -798,10 +802,7 @@ __device__ __forceinline__ int fuse_point(const spslam_fuse_problem& F, const sp
     dot = __dadd_rn(dot, __dmul_rn((double)PO[1], (double)p.normal[1]));
     dot = __dadd_rn(dot, __dmul_rn((double)PO[2], (double)p.normal[2]));
     if (dot < __dmul_rn(0.5, (double)dist)) return SPSLAM_FUSE_VIEW_ANGLE;  // doubles, no division (:884)
-    // PredictScale(dist3D, pKF), as local_window_kernel has it
-    const float ratio = __fdiv_rn(p.max_dist, dist);
-    const int n = (int)ceilf(__fdiv_rn((float)log((double)ratio), P.log_scale_factor));
-    *level = n < 0 ? 0 : (n >= P.n_levels ? P.n_levels - 1 : n);
+    *level = predict_scale(p.max_dist, dist, P.log_scale_factor, P.n_levels);  // PredictScale(dist3D, pKF)
     const FuseProbe q{u, v, ur, __fmul_rn(P.th, level_entry(g.scale, *level)), *level,
                       *(const uint4*)p.desc, *(const uint4*)(p.desc + 16)};
     int x0, x1, y0, y1;

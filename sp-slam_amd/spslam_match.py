@@ -17,6 +17,18 @@ PROJ_FRAME_DTYPE = np.dtype([("Tcw", "<f4", 16), ("Tlw", "<f4", 16), ("point_off
 assert PROJ_FRAME_DTYPE.itemsize == 144
 
 
+def _ptr(a):
+    """The address of an array, None for an absent or empty one."""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _current_frame(keys_un, desc, uright, grid_off, grid_idx):
+    """The current frame of a window search's host form as contiguous arrays of the C types."""
+    return (np.ascontiguousarray(keys_un, spslam_gpu.KEYPOINT_DTYPE),
+            np.ascontiguousarray(desc, np.uint8).reshape(-1, 32), np.ascontiguousarray(uright, np.float32),
+            np.ascontiguousarray(grid_off, np.int32), np.ascontiguousarray(grid_idx, np.int32))
+
+
 class MatchParams(ctypes.Structure):
     _fields_ = [("th", ctypes.c_float), ("mono", ctypes.c_int), ("check_orientation", ctypes.c_int),
                 ("retry_below", ctypes.c_int)]
@@ -46,17 +58,12 @@ class Matcher:
     def __call__(self, frame, points, keys_un, desc, uright, grid_off, grid_idx):
         fr = np.ascontiguousarray(frame, PROJ_FRAME_DTYPE).reshape(())
         pts = np.ascontiguousarray(points, PROJ_POINT_DTYPE)
-        k = np.ascontiguousarray(keys_un, spslam_gpu.KEYPOINT_DTYPE)
-        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
-        ur = np.ascontiguousarray(uright, np.float32)
-        go = np.ascontiguousarray(grid_off, np.int32)
-        gi = np.ascontiguousarray(grid_idx, np.int32)
+        k, d, ur, go, gi = _current_frame(keys_un, desc, uright, grid_off, grid_idx)
         n = len(k)
         match = np.zeros(max(n, 1), np.int32)
         nm = ctypes.c_int(0)
-        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
         self.ex._check(self.ex.lib.spslam_search_by_projection(
-            self.ex.ctx, fr.ctypes.data, ptr(pts), ptr(k), ptr(d), ptr(ur), n, go.ctypes.data, ptr(gi),
+            self.ex.ctx, fr.ctypes.data, _ptr(pts), _ptr(k), _ptr(d), _ptr(ur), n, go.ctypes.data, _ptr(gi),
             ctypes.byref(self.params), match.ctypes.data, ctypes.byref(nm)))
         return match[:n], nm.value
 
@@ -100,19 +107,14 @@ class LocalMatcher:
     def __call__(self, frame, points, keys_un, desc, uright, grid_off, grid_idx, taken=None):
         fr = np.ascontiguousarray(frame, LOCAL_FRAME_DTYPE).reshape(())
         pts = np.ascontiguousarray(points, LOCAL_POINT_DTYPE)
-        k = np.ascontiguousarray(keys_un, spslam_gpu.KEYPOINT_DTYPE)
-        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
-        ur = np.ascontiguousarray(uright, np.float32)
-        go = np.ascontiguousarray(grid_off, np.int32)
-        gi = np.ascontiguousarray(grid_idx, np.int32)
+        k, d, ur, go, gi = _current_frame(keys_un, desc, uright, grid_off, grid_idx)
         tk = None if taken is None else np.ascontiguousarray(taken, np.uint8)
         n = len(k)
         match = np.zeros(max(n, 1), np.int32)
         inv = np.zeros(max(len(pts), 1), np.uint8)
         nm = ctypes.c_int(0)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
         self.ex._check(self.ex.lib.spslam_search_local_points(
-            self.ex.ctx, fr.ctypes.data, ptr(pts), ptr(k), ptr(d), ptr(ur), n, go.ctypes.data, ptr(gi), ptr(tk),
+            self.ex.ctx, fr.ctypes.data, _ptr(pts), _ptr(k), _ptr(d), _ptr(ur), n, go.ctypes.data, _ptr(gi), _ptr(tk),
             ctypes.byref(self.params), match.ctypes.data, ctypes.byref(nm), inv.ctypes.data))
         return match[:n], nm.value, inv[:len(pts)].astype(bool)
 
@@ -160,18 +162,13 @@ class FuseSearch:
     def __call__(self, Tcw, points, keys_un, desc, uright, grid_off, grid_idx, skip=None):
         T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
         pts = np.ascontiguousarray(points, LOCAL_POINT_DTYPE)
-        k = np.ascontiguousarray(keys_un, spslam_gpu.KEYPOINT_DTYPE)
-        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
-        ur = np.ascontiguousarray(uright, np.float32)
-        go = np.ascontiguousarray(grid_off, np.int32)
-        gi = np.ascontiguousarray(grid_idx, np.int32)
+        k, d, ur, go, gi = _current_frame(keys_un, desc, uright, grid_off, grid_idx)
         sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
         res = np.zeros(max(len(pts), 1), FUSE_RESULT_DTYPE)
         nf = ctypes.c_int(0)
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
         self.ex._check(self.ex.lib.spslam_fuse_search(
-            self.ex.ctx, T.ctypes.data, ptr(pts), len(pts), ptr(k), ptr(d), ptr(ur), len(k), go.ctypes.data, ptr(gi),
-            ptr(sk), ctypes.byref(self.params), res.ctypes.data, ctypes.byref(nf)))
+            self.ex.ctx, T.ctypes.data, _ptr(pts), len(pts), _ptr(k), _ptr(d), _ptr(ur), len(k), go.ctypes.data,
+            _ptr(gi), _ptr(sk), ctypes.byref(self.params), res.ctypes.data, ctypes.byref(nf)))
         return res[:len(pts)], nf.value
 
     def batch_device(self, n_problems, d_problems, d_points, max_points, d_keys_un, d_desc, d_uright, d_grid_off,
@@ -219,10 +216,9 @@ class PointRefresh:
         d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         assert len(k) % cap == 0 and len(d) == len(k)
         status = np.full(max(len(rw), 1), 0xEE, np.uint8)
-        ptr = lambda x: x.ctypes.data if x is not None and x.size else None  # noqa: E731
-        m = PointRefreshMap(points=ptr(pts), **{name: ptr(a[name]) for name, _ in REFRESH_MAP_TABLES})
-        rc = self.ex.lib.spslam_map_points_refresh(self.ex.ctx, ctypes.byref(m), len(a["kf_slot"]), len(pts), ptr(rw),
-                                                   len(rw), what, ptr(k), ptr(d), cap, len(k) // cap,
+        m = PointRefreshMap(points=_ptr(pts), **{name: _ptr(a[name]) for name, _ in REFRESH_MAP_TABLES})
+        rc = self.ex.lib.spslam_map_points_refresh(self.ex.ctx, ctypes.byref(m), len(a["kf_slot"]), len(pts), _ptr(rw),
+                                                   len(rw), what, _ptr(k), _ptr(d), cap, len(k) // cap,
                                                    status.ctypes.data)
         if rc != ERR_CAPACITY:
             self.ex._check(rc)
@@ -292,9 +288,8 @@ class _TriHost:
                   np.ascontiguousarray(kf["fv"]["nodes"], np.uint32),
                   np.ascontiguousarray(kf["fv"]["start"], np.int32),
                   np.ascontiguousarray(kf["fv"]["features"], np.int32)]
-        ptr = lambda x: x.ctypes.data if x.size else None  # noqa: E731
         T = np.asarray(kf["Tcw"], np.float32).reshape(-1, 4)[:3].reshape(12)
-        self.rec = TriKeyframe(*[ptr(x) for x in self.a], n, len(self.a[6]), (ctypes.c_float * 12)(*T.tolist()),
+        self.rec = TriKeyframe(*[_ptr(x) for x in self.a], n, len(self.a[6]), (ctypes.c_float * 12)(*T.tolist()),
                                (ctypes.c_float * 3)(*np.asarray(kf["Ow"], np.float32).tolist()), 0)
 
 

@@ -9,6 +9,8 @@ import pathlib
 
 import numpy as np
 
+from matcher_ref import f32, rotation_bin, three_maxima
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 VOCAB_PARTS = [ROOT / "tests" / "golden" / f"vocab_k6_l6.part{i}.txt.gz" for i in range(3)]
 POP = np.array([bin(i).count("1") for i in range(256)], np.int32)
@@ -114,7 +116,6 @@ class PyVocab:
 
 def py_search_by_bow(kd, ka, has, kfv, fd, fa, ffv, nn_ratio=0.7, check_ori=True):
     """ORBmatcher::SearchByBoW (src/ORBmatcher.cc:159-288), restated in Python."""
-    f32 = np.float32
     match = np.full(len(fd), -1, np.int32)
     hist = [[] for _ in range(30)]
     n = 0
@@ -140,32 +141,12 @@ def py_search_by_bow(kd, ka, has, kfv, fd, fa, ffv, nn_ratio=0.7, check_ori=True
             if b1 <= 50 and f32(b1) < f32(f32(nn_ratio) * f32(b2)):
                 match[bi] = i
                 if check_ori:
-                    rot = f32(f32(ka[i]) - f32(fa[bi]))
-                    if rot < 0:
-                        rot = f32(rot + f32(360.0))
-                    x = f32(rot * f32(1.0 / 30))
-                    bn = int(math.floor(abs(float(x)) + 0.5)) * (1 if x >= 0 else -1)  # roundf
-                    if bn == 30:
-                        bn = 0
-                    hist[bn].append(bi)
+                    hist[rotation_bin(ka[i], fa[bi])].append(bi)
                 n += 1
     if check_ori:
-        m1 = m2 = m3 = 0
-        i1 = i2 = i3 = -1
+        keep = three_maxima([len(h) for h in hist])
         for i in range(30):
-            s = len(hist[i])
-            if s > m1:
-                m3, m2, m1, i3, i2, i1 = m2, m1, s, i2, i1, i
-            elif s > m2:
-                m3, m2, i3, i2 = m2, s, i2, i
-            elif s > m3:
-                m3, i3 = s, i
-        if m2 < f32(0.1) * f32(m1):
-            i2 = i3 = -1
-        elif m3 < f32(0.1) * f32(m1):
-            i3 = -1
-        for i in range(30):
-            if i in (i1, i2, i3):
+            if i in keep:
                 continue
             for j in hist[i]:
                 match[j] = -1

@@ -13,13 +13,10 @@ import functools
 import numpy as np
 
 import fuse_ref as FR
+from matcher_ref import f32 as _f
 
 PTS_PER_GROUP = 64  # points per workgroup of fuse_search_kernel (256 threads, 4 lanes per point)
 EYE = np.eye(4, dtype=np.float32).reshape(16)
-
-
-def _f(x):
-    return np.float32(x)
 
 
 @functools.lru_cache(maxsize=None)

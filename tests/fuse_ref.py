@@ -25,12 +25,11 @@ geo: [fx, fy, cx, cy, bf, min_x, max_x, min_y, max_y, grid inverse x, y, mvScale
 test_oracle_match.make_pairs builds it (the Frame's float bounds).
 """
 import ctypes
-import math
-from fractions import Fraction
 
 import numpy as np
 
 import point_refresh_ref
+from matcher_ref import descriptor_distance, f32 as _f, fma, mat3, round_f32  # noqa: F401 (other files import these from here)
 
 SEARCHED, SKIPPED, BEHIND, OUTSIDE_IMAGE, OUT_OF_RANGE, VIEW_ANGLE, NO_CANDIDATES = range(7)
 TH_LOW = 50
@@ -38,56 +37,6 @@ RESULT_DTYPE = np.dtype([("best_idx", "<i4"), ("best_dist", "<i2"), ("level", "u
 
 _libm = ctypes.CDLL("libm.so.6")
 _libm.logf.restype, _libm.logf.argtypes = ctypes.c_float, [ctypes.c_float]
-
-
-def _f(x):
-    return np.float32(x)
-
-
-def round_f32(fr):
-    """A rational rounded to the nearest float, ties to even (subnormals included)."""
-    if fr == 0:
-        return _f(0.0)
-    a = abs(fr)
-    e = a.numerator.bit_length() - a.denominator.bit_length()
-    if Fraction(2) ** e > a:
-        e -= 1                                                      # 2^e <= a < 2^(e+1)
-    q = max(e - 23, -149)
-    n = a / Fraction(2) ** q
-    fl = n.numerator // n.denominator
-    rem = n - fl
-    if rem > Fraction(1, 2) or (rem == Fraction(1, 2) and fl & 1):
-        fl += 1
-    return _f(math.copysign(math.ldexp(fl, q), fr))                 # exact in double (fl <= 2^24), inf on overflow
-
-
-def fma(a, b, c):
-    """fmaf(a, b, c): the exact a*b + c rounded once."""
-    a, b, c = float(_f(a)), float(_f(b)), float(_f(c))
-    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
-        with np.errstate(all="ignore"):
-            return _f(np.float64(a) * np.float64(b) + np.float64(c))   # inf / NaN propagate as in fmaf
-    return round_f32(Fraction(a) * Fraction(b) + Fraction(c))
-
-
-def mat3(T, x, c=None, transpose=False, sign=1.0):
-    """cv::Mat 3x3 * 3x1 (+ 3x1): each row summed in double, rounded once (the matcher family's reading)."""
-    T = np.asarray(T, np.float32).reshape(4, 4)
-    out = []
-    for r in range(3):
-        s = 0.0
-        for k in range(3):
-            s += float(T[k, r] if transpose else T[r, k]) * float(x[k])
-        s *= sign
-        if c is not None:
-            s += float(c[r])
-        out.append(_f(s))
-    return out
-
-
-def descriptor_distance(a, b):
-    """ORBmatcher::DescriptorDistance (:1647-1662): the popcount of the XOR."""
-    return int(np.unpackbits(np.bitwise_xor(np.asarray(a, np.uint8), np.asarray(b, np.uint8))).sum())
 
 
 def inv_level_sigma2(scale):

@@ -13,17 +13,11 @@ import math
 
 import numpy as np
 
+from matcher_ref import descriptor_distance, f32 as _f
+
 DESCRIPTOR, NORMAL_DEPTH = 1, 2
 DONE, UNTOUCHED, CAPACITY = 0, 1, 2
 MAX_OBS = 128
-
-
-def _f(x):
-    return np.float32(x)
-
-
-def descriptor_distance(a, b):
-    return int(np.unpackbits(np.bitwise_xor(np.asarray(a, np.uint8), np.asarray(b, np.uint8))).sum())
 
 
 def camera_center(Tcw):

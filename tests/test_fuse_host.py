@@ -15,10 +15,7 @@ import pytest
 
 import fuse_cases as FC
 import fuse_ref as FR
-
-
-def _f(x):
-    return np.float32(x)
+from matcher_ref import f32 as _f
 
 
 # ---------------------------------------------------------------- the whole call against the snapshot

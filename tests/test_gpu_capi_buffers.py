@@ -149,6 +149,90 @@ def test_search_by_projection_batch_device_grows_on_caller_stream(pair):
         ex.close()
 
 
+# ---------------------------------------------------------------------------
+# The three window searches' host forms stage the current frame through one helper (csrc/capi_ctx.h CurrentFrame):
+# its empty and one-entry ends, per host form, against that form's referee.
+
+def _edge_cuts(q, frame_key, points_key, k):
+    """q with no points; with no keypoints and an all-zero grid_off; with keypoint k alone (the points kept)."""
+    fr0 = q[frame_key].copy()
+    fr0["n_points"] = 0
+    none = _first_keypoints(q, 0)
+    cell = np.repeat(np.arange(len(q["go"]) - 1), np.diff(q["go"]))[list(q["gi"][:q["go"][-1]]).index(k)]
+    one = dict(q, kun=q["kun"][k:k + 1], desc=q["desc"][k:k + 1], ur=q["ur"][k:k + 1],
+               go=(np.arange(len(q["go"])) > cell).astype(np.int32), gi=np.zeros(1, np.int32))
+    assert not none["go"].any() and len(none["gi"]) == 0
+    return (("no points", dict(q, **{frame_key: fr0, points_key: q[points_key][:0]})), ("no keypoints", none),
+            ("one keypoint", one))
+
+
+@pytest.fixture(scope="module")
+def local_pair(pair):
+    from test_oracle_match import local_problems
+    return local_problems([pair], seed=23)[0]
+
+
+def _matched_keypoint(match):
+    """A keypoint the whole problem matches: the one-keypoint cut keeps it, so that cut has something to find."""
+    return int(np.flatnonzero(match >= 0)[0])
+
+
+def _local_matched_keypoint(q):
+    import oracle_match as OM
+    return _matched_keypoint(OM.search_local_points(q["lfr"], q["LP"], q["kun"], q["desc"], q["ur"], q["go"], q["gi"],
+                                                    q["geo"], taken=None)[0])
+
+
+def test_search_by_projection_host_form_at_its_empty_ends(pair):
+    import oracle_match as OM
+    import spslam_match
+    ex = _match_ctx()
+    try:
+        m = spslam_match.Matcher(ex)
+        q = pair
+        k = _matched_keypoint(OM.search_by_projection(q["fr"], q["P"], q["kun"], q["desc"], q["ur"], q["go"], q["gi"],
+                                                      q["geo"])[0])
+        for name, q in _edge_cuts(pair, "fr", "P", k):
+            mo, nmo, _ = OM.search_by_projection(q["fr"], q["P"], q["kun"], q["desc"], q["ur"], q["go"], q["gi"],
+                                                 q["geo"])
+            mg, nmg = m(q["fr"], q["P"], q["kun"], q["desc"], q["ur"], q["go"], q["gi"])
+            assert nmg == nmo and len(mg) == len(q["kun"]) and np.array_equal(mg, mo), name
+    finally:
+        ex.close()
+
+
+def test_search_local_points_host_form_at_its_empty_ends(local_pair):
+    import oracle_match as OM
+    import spslam_match
+    ex = _match_ctx()
+    try:
+        lm = spslam_match.LocalMatcher(ex)
+        for name, q in _edge_cuts(local_pair, "lfr", "LP", _local_matched_keypoint(local_pair)):  # taken absent
+            mo, nmo, ivo = OM.search_local_points(q["lfr"], q["LP"], q["kun"], q["desc"], q["ur"], q["go"], q["gi"],
+                                                  q["geo"], taken=None)
+            mg, nmg, ivg = lm(q["lfr"], q["LP"], q["kun"], q["desc"], q["ur"], q["go"], q["gi"], None)
+            assert nmg == nmo and len(mg) == len(q["kun"]) and np.array_equal(mg, mo), name
+            assert len(ivg) == len(q["LP"]) and np.array_equal(ivg, ivo), name
+    finally:
+        ex.close()
+
+
+def test_fuse_search_host_form_at_its_empty_ends(local_pair):
+    import fuse_ref as FR
+    import spslam_match
+    ex = _match_ctx()
+    try:
+        fs = spslam_match.FuseSearch(ex)
+        for name, q in _edge_cuts(local_pair, "lfr", "LP", _local_matched_keypoint(local_pair)):  # skip absent
+            want, want_nf = FR.snapshot_search(q["lfr"]["Tcw"], q["LP"], q["kun"], q["desc"], q["ur"], q["go"],
+                                               q["gi"], q["geo"])
+            res, nf = fs(q["lfr"]["Tcw"], q["LP"], q["kun"], q["desc"], q["ur"], q["go"], q["gi"])
+            assert len(res) == len(q["LP"]) and res.tobytes() == want.astype(res.dtype).tobytes(), name
+            assert nf == want_nf, name
+    finally:
+        ex.close()
+
+
 def test_bow_transform_grow_then_reuse():
     import bow_common as BC
     import spslam_bow

@@ -19,30 +19,9 @@ import oracle_ctypes
 import oracle_frame
 import oracle_match as OM
 import synth
+from matcher_ref import f32 as _f, fma, mat3, rotation_bin, three_maxima
 
 K = synth.TUM3
-
-
-def _f(x):
-    return np.float32(x)
-
-
-def _fma(a, b, c):
-    return _f(np.float64(_f(a)) * np.float64(_f(b)) + np.float64(_f(c)))
-
-
-def _mat3(T, x, c=None, transpose=False, sign=1.0):
-    T = np.asarray(T, np.float32).reshape(4, 4)
-    out = []
-    for r in range(3):
-        s = 0.0
-        for k in range(3):
-            s += float(T[k, r] if transpose else T[r, k]) * float(x[k])
-        s *= sign
-        if c is not None:
-            s += float(c[r])
-        out.append(_f(s))
-    return out
 
 
 def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True):
@@ -53,19 +32,19 @@ def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True)
     match, blocking = [-1] * n, [False] * n
     Tcw, Tlw = fr["Tcw"].reshape(4, 4), fr["Tlw"].reshape(4, 4)
     tcw, tlw = Tcw[:3, 3], Tlw[:3, 3]
-    twc = _mat3(Tcw, tcw, transpose=True, sign=-1.0)
-    tlc = _mat3(Tlw, twc, c=tlw)
+    twc = mat3(Tcw, tcw, transpose=True, sign=-1.0)
+    tlc = mat3(Tlw, twc, c=tlw)
     mb = _f(bf / fx)
     fwd = tlc[2] > mb and not mono
     bwd = -tlc[2] > mb and not mono
     hist = [[] for _ in range(30)]
     nm = 0
     for i, p in enumerate(P):
-        x3 = _mat3(Tcw, p["xw"], c=tcw)
+        x3 = mat3(Tcw, p["xw"], c=tcw)
         invz = _f(1.0 / float(x3[2]))
         if invz < 0:
             continue
-        u, v = _fma(_f(fx * x3[0]), invz, cx), _fma(_f(fy * x3[1]), invz, cy)
+        u, v = fma(_f(fx * x3[0]), invz, cx), fma(_f(fy * x3[1]), invz, cy)
         if u < minx or u > maxx or v < miny or v > maxy:
             continue
         o = int(p["octave"])
@@ -92,7 +71,7 @@ def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True)
             if match[k] >= 0 and blocking[k]:
                 continue
             if ur[k] > 0:
-                urp = _fma(-bf, invz, u)
+                urp = fma(-bf, invz, u)
                 if abs(_f(urp - ur[k])) > r:
                     continue
             d = OM.descriptor_distance(p["desc"], desc[k])
@@ -103,30 +82,9 @@ def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True)
             blocking[bi] = p["n_obs"] > 0
             nm += 1
             if check_ori:
-                rot = _f(p["angle"] - kun[bi]["angle"])
-                if rot < 0.0:
-                    rot = _f(rot + _f(360.0))
-                b = int(np.round(np.float64(_f(rot * _f(1.0 / 30)))))  # half-way cases away from zero below
-                x = float(_f(rot * _f(_f(1.0) / _f(30))))
-                b = int(np.floor(x + 0.5)) if x >= 0 else -int(np.floor(-x + 0.5))
-                hist[0 if b == 30 else b].append(bi)
+                hist[rotation_bin(p["angle"], kun[bi]["angle"])].append(bi)
     if check_ori:
-        m = [0, 0, 0]
-        ind = [-1, -1, -1]
-        for b in range(30):
-            s = len(hist[b])
-            if s > m[0]:
-                m = [s, m[0], m[1]]
-                ind = [b, ind[0], ind[1]]
-            elif s > m[1]:
-                m = [m[0], s, m[1]]
-                ind = [ind[0], b, ind[1]]
-            elif s > m[2]:
-                m[2], ind[2] = s, b
-        if m[1] < _f(_f(0.1) * _f(m[0])):
-            ind[1] = ind[2] = -1
-        elif m[2] < _f(_f(0.1) * _f(m[0])):
-            ind[2] = -1
+        ind = three_maxima([len(h) for h in hist])
         for b in range(30):
             if b not in ind:
                 for k in hist[b]:
@@ -241,10 +199,10 @@ def test_projection_expressions_match_gcc_march_native(tmp_path):
         xc, yc = rng.normal(size=2).astype(np.float32)
         invz = np.float32(1.0 / rng.uniform(0.3, 6.0))
         L.probe_proj(K["fx"], K["fy"], K["cx"], K["cy"], K["bf"], xc, yc, invz, out.ctypes.data)
-        u = _fma(_f(_f(K["fx"]) * xc), invz, K["cx"])
-        v = _fma(_f(_f(K["fy"]) * yc), invz, K["cy"])
+        u = fma(_f(_f(K["fx"]) * xc), invz, K["cx"])
+        v = fma(_f(_f(K["fy"]) * yc), invz, K["cy"])
         assert out[0] == u and out[1] == v
-        assert out[2] == _fma(-_f(K["bf"]), invz, u)
+        assert out[2] == fma(-_f(K["bf"]), invz, u)
 
 
 # ---------------------------------------------------------------- SearchLocalPoints
@@ -261,15 +219,15 @@ def py_search_local(fr, P, kun, desc, ur, go, gi, geo, taken, th=3.0, nn=0.8, vc
     match, tk = [-1] * n, [bool(t) for t in taken]
     Tcw = fr["Tcw"].reshape(4, 4)
     tcw = Tcw[:3, 3]
-    Ow = _mat3(Tcw, tcw, transpose=True, sign=-1.0)
+    Ow = mat3(Tcw, tcw, transpose=True, sign=-1.0)
     nm = 0
     inview = []
     for i, p in enumerate(P):
-        Pc = _mat3(Tcw, p["xw"], c=tcw)
+        Pc = mat3(Tcw, p["xw"], c=tcw)
         ok = False
         if Pc[2] >= 0:
             invz = _f(_f(1.0) / Pc[2])
-            u, v = _fma(_f(fx * Pc[0]), invz, cx), _fma(_f(fy * Pc[1]), invz, cy)
+            u, v = fma(_f(fx * Pc[0]), invz, cx), fma(_f(fy * Pc[1]), invz, cy)
             if minx <= u <= maxx and miny <= v <= maxy:
                 PO = [_f(p["xw"][k] - Ow[k]) for k in range(3)]
                 s = _f(PO[0] * PO[0])
@@ -291,7 +249,7 @@ def py_search_local(fr, P, kun, desc, ur, go, gi, geo, taken, th=3.0, nn=0.8, vc
         if th != 1.0:
             r = _f(r * _f(th))
         rs = _f(r * scale[lvl])
-        urp = _fma(-bf, invz, u)
+        urp = fma(-bf, invz, u)
         x0 = max(0, int(np.floor(_f(_f(_f(u - minx) - rs) * gix))))
         x1 = min(63, int(np.ceil(_f(_f(_f(u - minx) + rs) * gix))))
         y0 = max(0, int(np.floor(_f(_f(_f(v - miny) - rs) * giy))))

@@ -18,6 +18,7 @@ import pytest
 
 import triangulation_cases as TC
 import triangulation_ref as TR
+from matcher_ref import f32 as _f
 
 # Largest relative difference |x3D - x3D_64| / |x3D_64| between the restatement's Jacobi (float columns) and the
 # float64 numpy.linalg.svd null vector of the same float A, measured over every accepted (SPSLAM_TRI_NEW, SVD) match
@@ -25,10 +26,6 @@ import triangulation_ref as TR
 # conditioned differently from these.
 SVD_REL_MEASURED = 6.2e-7
 SVD_REL_BOUND = 4 * SVD_REL_MEASURED
-
-
-def _f(x):
-    return np.float32(x)
 
 
 @pytest.fixture(scope="module")

@@ -16,16 +16,13 @@ import numpy as np
 
 import bow_common as BC
 import triangulation_ref as TR
+from matcher_ref import f32 as _f
 
 GROUP = 8          # kTriGroup of triangulation_search_kernel: lanes per key-1 feature
 STEP = 20          # frame step of the real pairs: the baseline (0.08 m) is above mb = bf/fx (0.075 m), and both the
                    # SVD and the UnprojectStereo source occur
 SEQS = (0, 2)      # the sequences whose pairs give >= 20 matches at 200 features
 LIST_LENGTHS = (0, 1, GROUP - 1, GROUP, GROUP + 1, 64, 65)
-
-
-def _f(x):
-    return np.float32(x)
 
 
 @functools.lru_cache(maxsize=None)

@@ -38,10 +38,10 @@ import ctypes
 
 import numpy as np
 
-from fuse_ref import descriptor_distance, fma, mat3
+from matcher_ref import (HISTO, descriptor_distance, f32 as _f, fma, mat3,  # noqa: F401 (other files import these
+                         rotation_bin, three_maxima)                        # from here)
 
 TH_LOW = 50
-HISTO = 30
 NEW, NO_MATCH, LOW_PARALLAX, W_ZERO, BEHIND_1, BEHIND_2, REPROJ_1, REPROJ_2, ZERO_DIST, SCALE = range(10)
 FROM_SVD, FROM_STEREO_1, FROM_STEREO_2 = range(3)
 SEARCHED, SKIPPED, SHORT_BASELINE = range(3)
@@ -53,10 +53,6 @@ JACOBI_EPS = 2.0 ** -22          # 2*FLT_EPSILON, OpenCV's choice for float matr
 _libm = ctypes.CDLL("libm.so.6")
 _libm.atan2f.restype, _libm.atan2f.argtypes = ctypes.c_float, [ctypes.c_float, ctypes.c_float]
 _libm.cosf.restype, _libm.cosf.argtypes = ctypes.c_float, [ctypes.c_float]
-
-
-def _f(x):
-    return np.float32(x)
 
 
 def _d(x):
@@ -91,32 +87,6 @@ def dot3(a, b):
     for k in range(3):
         s = s + _d(a[k]) * _d(b[k])
     return s
-
-
-def rotation_bin(a1, a2):
-    rot = _f(a1) - _f(a2)
-    if rot < 0:
-        rot = rot + _f(360.0)
-    x = rot * _f(1.0 / HISTO)
-    bn = int(np.floor(abs(float(x)) + 0.5)) * (1 if x >= 0 else -1)   # roundf
-    return 0 if bn == HISTO else bn
-
-
-def three_maxima(counts):
-    m1 = m2 = m3 = 0
-    i1 = i2 = i3 = -1
-    for i, s in enumerate(counts):
-        if s > m1:
-            m3, m2, m1, i3, i2, i1 = m2, m1, s, i2, i1, i
-        elif s > m2:
-            m3, m2, i3, i2 = m2, s, i2, i
-        elif s > m3:
-            m3, i3 = s, i
-    if m2 < _f(0.1) * _f(m1):
-        i2 = i3 = -1
-    elif m3 < _f(0.1) * _f(m1):
-        i3 = -1
-    return i1, i2, i3
 
 
 # ---------------------------------------------------------------- SearchForTriangulation
