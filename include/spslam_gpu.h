@@ -1033,6 +1033,179 @@ int spslam_search_for_triangulation(spslam_ctx* ctx, const spslam_tri_keyframe* 
 int spslam_triangulate(spslam_ctx* ctx, const spslam_tri_keyframe* kf1, const spslam_tri_keyframe* kf2,
                        const int32_t* matched_pairs, int n_matches, spslam_tri_result* results, int* n_new);
 
+/* ---------------------------------------------------------------- LocalMapping: covisibility graph, the cullings
+ * KeyFrame::UpdateConnections (src/KeyFrame.cc:306-396) with AddConnection
+ * (:128-141) and UpdateBestCovisibles (:143-162); LocalMapping::KeyFrameCulling
+ * (src/LocalMapping.cc:644-711, RGB-D branch) and LocalMapping::MapPointCulling
+ * (:182-217).  Index work on the tables spslam_local_map and
+ * spslam_point_refresh_map define.  Keyframe indices and point rows are local to
+ * a sequence: keyframe k of a problem is entry kf_base + k of the keyframe
+ * tables, row r is entry row_base + r of the point tables, so many sequences
+ * share one call.  Keyframes are walked in ascending index where the reference
+ * has pointer order, as everywhere at this ABI; index 0 of a sequence is
+ * mnId == 0.  The device forms trust their tables: every index must lie inside
+ * its table (the host forms check them). */
+typedef struct spslam_covis_map {
+    const int32_t* match_off;   /* CSR (keyframes + 1), absolute offsets into match_row */
+    const int32_t* match_row;   /* GetMapPointMatches in keypoint order: the point's row or -1 */
+    const int32_t* obs_off;     /* CSR (rows + 1), absolute offsets */
+    const int32_t* obs_kf;      /* observer keyframes, ascending (MapPoint::GetObservations) */
+    const int32_t* obs_kp;      /* that observation's keypoint index (KeyFrameCulling only) */
+    const int32_t* kf_slot;     /* per keyframe: its slot in d_keys_un / d_uright / d_depth (KeyFrameCulling only) */
+    const uint8_t* point_bad;   /* MapPoint::isBad (may be NULL: none) */
+    const spslam_local_point* points;  /* n_obs = MapPoint::Observations() (the cullings only) */
+} spslam_covis_map;
+
+/* The binding's mirror of the reference's covisibility members, device resident
+ * and persistent across calls.  Keyframe k's rows are at (kf_base + k) * stride. */
+typedef struct spslam_covis_graph {
+    int32_t* weights;           /* stride per keyframe: mConnectedKeyFrameWeights by keyframe index, 0 = absent */
+    int32_t* ordered;           /* stride per keyframe: mvpOrderedConnectedKeyFrames; entries past n_ordered are kept */
+    int32_t* ordered_w;         /* stride per keyframe: mvOrderedWeights */
+    int32_t* n_ordered;         /* per keyframe */
+    int32_t* covis;             /* 10 per keyframe: GetBestCovisibilityKeyFrames(10), -1 padded: spslam_local_map.covis.
+                                   Rewritten whenever that keyframe's ordered list is rewritten */
+    int32_t* parent;            /* per keyframe: mpParent, -1 = none: spslam_local_map.parent */
+    uint8_t* first_connection;  /* per keyframe: mbFirstConnection */
+    int32_t stride;             /* >= every problem's n_kf */
+    int32_t pad;
+} spslam_covis_graph;
+
+typedef struct spslam_covis_problem {
+    int32_t kf_base, row_base;
+    int32_t kf;                 /* the keyframe whose UpdateConnections runs / mpCurrentKeyFrame of the culling */
+    int32_t n_kf;               /* keyframes of this sequence, 1 .. 1024 */
+} spslam_covis_problem;         /* 16 bytes */
+
+#define SPSLAM_COVIS_MAX_KF 1024
+#define SPSLAM_COVIS_BEST 10         /* entries of covis per keyframe */
+#define SPSLAM_COVIS_UPDATED 0
+#define SPSLAM_COVIS_EMPTY 1         /* KFcounter.empty() (:340): nothing of the graph is written */
+
+typedef struct spslam_covis_result {
+    int32_t status;             /* SPSLAM_COVIS_* */
+    int32_t n_ordered;          /* the keyframe's ordered list after the call (EMPTY: 0, the list itself is kept) */
+    int32_t new_parent;         /* mpParent set by the first connection (:388-393), -1: none set.  AddChild stays
+                                   with the caller: it appends kf to new_parent's children */
+    int32_t n_resorted;         /* selected keyframes whose weight changed, i.e. UpdateBestCovisibles ran */
+} spslam_covis_result;          /* 16 bytes */
+
+/* UpdateConnections of problem p's keyframe, one workgroup per problem:
+ *   counts (:319-337): every match row of kf that is not -1 and not bad adds one to each of its observers but kf;
+ *   all zero (:340): SPSLAM_COVIS_EMPTY;
+ *   selection (:345-369): every keyframe with count >= th (the reference's 15); none: the first strict maximum in
+ *     ascending index;
+ *   kf's own state (:384-386): its whole weights row becomes the counts (those below th too), its ordered list the
+ *     selected keyframes by weight descending, the higher index first on equal weight (sort, then push_front);
+ *   every selected keyframe j (AddConnection): weights[j][kf] already equal to the count: nothing of j changes.
+ *     Otherwise it is written and j's ordered list is rebuilt from every non-zero entry of its row, in the same
+ *     order (UpdateBestCovisibles): that brings in entries below th which j's own UpdateConnections left out;
+ *   first connection (:388-393): first_connection[kf] set and kf != 0: parent[kf] = ordered[kf][0], flag cleared.
+ * CONTRACT: a call holds at most one problem per sequence (a problem writes other keyframes' rows).  Several
+ * keyframes of one sequence are successive calls on one stream. */
+int spslam_covis_update_connections_batch_device(spslam_ctx* ctx, int n_problems,
+                                                 const spslam_covis_problem* d_problems,
+                                                 const spslam_covis_map* map, const spslam_covis_graph* graph, int th,
+                                                 spslam_covis_result* d_results, void* hip_stream);
+
+/* One problem on host arrays (map's and graph's pointers too) at bases 0: n_kf keyframes, n_rows point rows.  The
+ * graph arrays are rewritten in place.  map: obs_kp, kf_slot and points are not read. */
+int spslam_covis_update_connections(spslam_ctx* ctx, const spslam_covis_map* map, int n_kf, int n_rows, int kf, int th,
+                                    const spslam_covis_graph* graph, spslam_covis_result* result);
+
+/* KeyFrameCulling for problem p's current keyframe, one workgroup per problem.  The candidates are the keyframe's
+ * ordered list in the graph (GetVectorCovisibleKeyFrames), read once at the start and taken in order:
+ *   new_plane[kf] set (:650): problem status SPSLAM_CULL_NEW_PLANE, no candidates;
+ *   candidate index 0 or new_plane[c] set (:658): SPSLAM_CULL_SKIPPED;
+ *   otherwise, over its keypoints with a row that is not (effectively) bad: depth > th_depth || depth < 0: not
+ *     counted; n_mps++; effective Observations() > th_obs: the observers other than c and not culled earlier in this
+ *     call whose octave at their obs_kp is <= this keypoint's octave + 1 are counted, th_obs or more make the
+ *     keypoint redundant;
+ *   verdict: (double)n_redundant > 0.9 * (double)n_mps;
+ *   a culled candidate with not_erase set: SPSLAM_CULL_DEFERRED (mbToBeErased, KeyFrame.cc:476-480), nothing
+ *     changes for later candidates; any other culled candidate: SPSLAM_CULL_CULLED, and it joins the call's
+ *     culled set.
+ * "Effective" carries KeyFrame::SetBadFlag's EraseObservation loop (KeyFrame.cc:486-488, MapPoint.cc:111-137)
+ * forward without writing the map: a point's Observations() is n_obs minus, per observer in the culled set, 2 when
+ * that observation's uright >= 0 and else 1; the point is bad when point_bad says so, or when it has a culled
+ * observer and that value is <= 2.
+ * CONTRACT: the match rows and the observer lists agree with each other; a keyframe's match list is no longer than
+ * cap.  Nothing of the map or the graph is written: the caller applies SetBadFlag to the culled ones in order. */
+#define SPSLAM_CULL_KEPT 0
+#define SPSLAM_CULL_CULLED 1
+#define SPSLAM_CULL_DEFERRED 2
+#define SPSLAM_CULL_SKIPPED 3
+#define SPSLAM_CULL_RAN 0            /* problem status */
+#define SPSLAM_CULL_NEW_PLANE 1      /* problem status */
+
+typedef struct spslam_cull_problem {
+    int32_t kf_base, row_base;
+    int32_t kf;                 /* mpCurrentKeyFrame */
+    int32_t n_kf;               /* 1 .. 1024 */
+    int32_t out_offset;         /* candidate q's record at d_records[out_offset + q] */
+    int32_t pad[3];
+} spslam_cull_problem;          /* 32 bytes */
+
+typedef struct spslam_cull_record {
+    int32_t kf;                 /* the candidate */
+    int32_t n_mps;              /* nMPs */
+    int32_t n_redundant;        /* nRedundantObservations */
+    int32_t status;             /* SPSLAM_CULL_KEPT / CULLED / DEFERRED / SKIPPED */
+} spslam_cull_record;           /* 16 bytes */
+
+typedef struct spslam_cull_summary {
+    int32_t n_candidates;       /* records written */
+    int32_t status;             /* SPSLAM_CULL_RAN / SPSLAM_CULL_NEW_PLANE */
+} spslam_cull_summary;
+
+typedef struct spslam_cull_params {
+    float th_depth;             /* mThDepth */
+    int32_t th_obs;             /* thObs (3) */
+} spslam_cull_params;
+
+/* d_keys_un / d_uright / d_depth: the frame stage's layouts, slot s at s * cap.  d_new_plane: one byte per keyframe
+ * (mbNewPlane); d_not_erase: one byte per keyframe (mbNotErase), may be NULL.  Only graph->ordered, n_ordered and
+ * stride are read. */
+int spslam_keyframe_culling_batch_device(spslam_ctx* ctx, int n_problems, const spslam_cull_problem* d_problems,
+                                         const spslam_covis_map* map, const spslam_covis_graph* graph,
+                                         const spslam_keypoint* d_keys_un, const float* d_uright, const float* d_depth,
+                                         int cap, const uint8_t* d_new_plane, const uint8_t* d_not_erase,
+                                         const spslam_cull_params* params, spslam_cull_record* d_records,
+                                         spslam_cull_summary* d_summaries, void* hip_stream);
+
+/* One problem on host arrays at bases 0: n_kf keyframes, n_rows rows, n_slots keyframe slots of cap keypoints;
+ * ordered / n_ordered: the current keyframe's list.  records: room for n_ordered entries. */
+int spslam_keyframe_culling(spslam_ctx* ctx, const spslam_covis_map* map, int n_kf, int n_rows, int kf,
+                            const int32_t* ordered, int n_ordered, const spslam_keypoint* keys_un, const float* uright,
+                            const float* depth, int cap, int n_slots, const uint8_t* new_plane,
+                            const uint8_t* not_erase, const spslam_cull_params* params, spslam_cull_record* records,
+                            spslam_cull_summary* summary);
+
+/* MapPointCulling: per entry k of mlpRecentAddedMapPoints (rows[k], an absolute row of the point tables) the first
+ * branch of :198-215 that holds, with cur_kf_id[k] = mpCurrentKeyFrame->mnId of the entry's sequence.  Applying the
+ * verdicts (SetBadFlag, erase from the list) stays with the caller. */
+#define SPSLAM_POINT_CULL_KEEP 0
+#define SPSLAM_POINT_CULL_DROP 1        /* isBad(): erased from the list only */
+#define SPSLAM_POINT_CULL_BAD_RATIO 2   /* (float)mnFound / mnVisible < 0.25f */
+#define SPSLAM_POINT_CULL_BAD_OBS 3     /* id difference >= 2 and Observations() <= th_obs */
+#define SPSLAM_POINT_CULL_EXPIRED 4     /* id difference >= 3 */
+
+typedef struct spslam_point_cull_map {  /* per point row */
+    const int32_t* found;       /* mnFound */
+    const int32_t* visible;     /* mnVisible */
+    const int32_t* first_kf;    /* mnFirstKFid */
+    const uint8_t* point_bad;   /* may be NULL */
+    const spslam_local_point* points;  /* n_obs */
+} spslam_point_cull_map;
+
+int spslam_map_point_culling_batch_device(spslam_ctx* ctx, const spslam_point_cull_map* map, const int32_t* d_rows,
+                                          const int32_t* d_cur_kf_id, int n, int th_obs, uint8_t* d_verdict,
+                                          void* hip_stream);
+
+/* The same on host arrays of n_rows rows; cur_kf_id: one id for the whole list. */
+int spslam_map_point_culling(spslam_ctx* ctx, const spslam_point_cull_map* map, int n_rows, const int32_t* rows, int n,
+                             int cur_kf_id, int th_obs, uint8_t* verdict);
+
 /* ---------------------------------------------------------------- input images
  * Tracking::GrabImageRGBD's image preparation (src/Tracking.cc:208-229), the
  * first kernel of a step:

@@ -29,6 +29,7 @@
 #include "track_launch.h"
 #include "grab_launch.h"
 #include "triangulate_launch.h"
+#include "covis_launch.h"
 
 using namespace spslam;
 

@@ -1,8 +1,11 @@
 // C ABI (include/spslam_gpu.h), LocalMapping's ORBmatcher side: spslam_fuse_search[_batch_device] (SearchInNeighbors'
 // Fuse), spslam_map_points_refresh[_batch_device] (ComputeDistinctiveDescriptors, UpdateNormalAndDepth) and
 // CreateNewMapPoints: spslam_search_for_triangulation[_batch_device], spslam_triangulate[_batch_device],
-// spslam_create_new_points_batch_device, with TriStage, the staging of their host forms.
+// spslam_create_new_points_batch_device, with TriStage, the staging of their host forms; and the covisibility side:
+// spslam_covis_update_connections[_batch_device] (KeyFrame::UpdateConnections), spslam_keyframe_culling[_batch_device]
+// and spslam_map_point_culling[_batch_device], whose host forms check their indices with covis_check.h.
 #include "capi_ctx.h"
+#include "covis_check.h"
 
 #include <cmath>
 #include <cstring>
@@ -344,6 +347,208 @@ int spslam_triangulate(spslam_ctx* c, const spslam_tri_keyframe* kf1, const spsl
     if ((rc = ts.st.close())) return rc;
     HIP_CHECK(c, hipStreamSynchronize(c->stream));
     for (int q = 0; q < n_matches; q++) results[q] = rec[matched_pairs[2 * q]];
+    return SPSLAM_OK;
+}
+
+// ---------------------------------------------------------------- covisibility graph, the cullings
+int spslam_covis_update_connections_batch_device(spslam_ctx* c, int n_problems, const spslam_covis_problem* d_problems,
+                                                 const spslam_covis_map* map, const spslam_covis_graph* graph, int th,
+                                                 spslam_covis_result* d_results, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_problems < 1 || !d_problems || !map || !graph || th < 1 || !d_results || !map->match_off ||
+        !map->match_row || !map->obs_off || !map->obs_kf)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_covis_update_connections_batch_device");
+    if (const char* e = covis_check_graph(*graph, 1))
+        return fail(c, SPSLAM_ERR_ARG, "spslam_covis_update_connections_batch_device: %s", e);
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, covis_update_connections_launch(n_problems, d_problems, *map, *graph, th, d_results,
+                                                 (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_covis_update_connections(spslam_ctx* c, const spslam_covis_map* map, int n_kf, int n_rows, int kf, int th,
+                                    const spslam_covis_graph* graph, spslam_covis_result* result) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!map || !graph || !result || th < 1)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_covis_update_connections");
+    const char* e = covis_check_map(*map, n_kf, n_rows, false, 0, 0);
+    if (!e) e = covis_check_graph(*graph, n_kf);
+    if (!e && (kf < 0 || kf >= n_kf)) e = "kf outside the keyframes";
+    if (e) return fail(c, SPSLAM_ERR_ARG, "spslam_covis_update_connections: %s", e);
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const spslam_covis_map& m = *map;
+    const spslam_covis_graph& g = *graph;
+    const size_t K = (size_t)n_kf, R = (size_t)n_rows, NM = (size_t)m.match_off[n_kf], NO = (size_t)m.obs_off[n_rows],
+                 W = K * (size_t)g.stride * 4;
+    const auto one = [](size_t x) { return std::max(x, (size_t)1); };
+    const spslam_covis_problem P{0, 0, kf, n_kf};
+    enum { kMatchOff, kMatchRow, kObsOff, kObsKf, kBad, kWeights, kOrdered, kOrderedW, kNOrdered, kCovis, kParent,
+           kFirst, kProblem, kResult };
+    Stage st(c);
+    if (int rc = st.open({{m.match_off, (K + 1) * 4}, {m.match_row, NM * 4, one(NM) * 4}, {m.obs_off, (R + 1) * 4},
+                           {m.obs_kf, NO * 4, one(NO) * 4}, {m.point_bad, m.point_bad ? R : 0, one(R)},
+                           {g.weights, W}, {g.ordered, W}, {g.ordered_w, W}, {g.n_ordered, K * 4},
+                           {g.covis, K * SPSLAM_COVIS_BEST * 4}, {g.parent, K * 4}, {g.first_connection, K},
+                           {&P, sizeof P}, sizeof(spslam_covis_result)}))
+        return rc;
+    spslam_covis_map dm{};
+    dm.match_off = st.slot<int32_t>(kMatchOff);
+    dm.match_row = st.slot<int32_t>(kMatchRow);
+    dm.obs_off = st.slot<int32_t>(kObsOff);
+    dm.obs_kf = st.slot<int32_t>(kObsKf);
+    dm.point_bad = m.point_bad ? st.slot<uint8_t>(kBad) : nullptr;
+    spslam_covis_graph dg{};
+    dg.weights = st.slot<int32_t>(kWeights);
+    dg.ordered = st.slot<int32_t>(kOrdered);
+    dg.ordered_w = st.slot<int32_t>(kOrderedW);
+    dg.n_ordered = st.slot<int32_t>(kNOrdered);
+    dg.covis = st.slot<int32_t>(kCovis);
+    dg.parent = st.slot<int32_t>(kParent);
+    dg.first_connection = st.slot<uint8_t>(kFirst);
+    dg.stride = g.stride;
+    int rc = spslam_covis_update_connections_batch_device(c, 1, st.slot<spslam_covis_problem>(kProblem), &dm, &dg, th,
+                                                          st.slot<spslam_covis_result>(kResult), c->stream);
+    if (rc) return rc;
+    void* const host[] = {g.weights, g.ordered, g.ordered_w, g.n_ordered, g.covis, g.parent, g.first_connection,
+                          result};
+    const int slot[] = {kWeights, kOrdered, kOrderedW, kNOrdered, kCovis, kParent, kFirst, kResult};
+    const size_t bytes[] = {W, W, W, K * 4, K * SPSLAM_COVIS_BEST * 4, K * 4, K, sizeof(spslam_covis_result)};
+    for (int a = 0; a < 8; a++)
+        HIP_CHECK(c, hipMemcpyAsync(host[a], st.slot<void>(slot[a]), bytes[a], hipMemcpyDeviceToHost, c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+int spslam_keyframe_culling_batch_device(spslam_ctx* c, int n_problems, const spslam_cull_problem* d_problems,
+                                         const spslam_covis_map* map, const spslam_covis_graph* graph,
+                                         const spslam_keypoint* d_keys_un, const float* d_uright, const float* d_depth,
+                                         int cap, const uint8_t* d_new_plane, const uint8_t* d_not_erase,
+                                         const spslam_cull_params* params, spslam_cull_record* d_records,
+                                         spslam_cull_summary* d_summaries, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (n_problems < 1 || !d_problems || !map || !graph || !d_keys_un || !d_uright || !d_depth || cap < 1 ||
+        cap > (1 << 20) || !d_new_plane || !params || params->th_obs < 1 || !d_records || !d_summaries ||
+        !map->match_off || !map->match_row || !map->obs_off || !map->obs_kf || !map->obs_kp || !map->kf_slot ||
+        !map->points || !graph->ordered || !graph->n_ordered || graph->stride < 1)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_keyframe_culling_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, keyframe_culling_launch(n_problems, d_problems, *map, *graph, CullFrames{d_keys_un, d_uright, d_depth, cap},
+                                         d_new_plane, d_not_erase, *params, d_records, d_summaries,
+                                         (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_keyframe_culling(spslam_ctx* c, const spslam_covis_map* map, int n_kf, int n_rows, int kf,
+                            const int32_t* ordered, int n_ordered, const spslam_keypoint* keys_un, const float* uright,
+                            const float* depth, int cap, int n_slots, const uint8_t* new_plane,
+                            const uint8_t* not_erase, const spslam_cull_params* params, spslam_cull_record* records,
+                            spslam_cull_summary* summary) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!map || !new_plane || !params || !summary || (n_ordered > 0 && !records) ||
+        ((size_t)std::max(n_slots, 0) * std::max(cap, 0) && (!keys_un || !uright || !depth)))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_keyframe_culling");
+    const char* e = covis_check_map(*map, n_kf, n_rows, true, cap, n_slots);
+    if (!e) e = covis_check_candidates(ordered, n_ordered, n_kf);
+    if (!e && (kf < 0 || kf >= n_kf)) e = "kf outside the keyframes";
+    if (e) return fail(c, SPSLAM_ERR_ARG, "spslam_keyframe_culling: %s", e);
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const spslam_covis_map& m = *map;
+    const size_t K = (size_t)n_kf, R = (size_t)n_rows, NM = (size_t)m.match_off[n_kf], NO = (size_t)m.obs_off[n_rows],
+                 S = (size_t)n_slots * cap, NC = (size_t)n_ordered, Pt = sizeof(spslam_local_point),
+                 Kp = sizeof(spslam_keypoint);
+    const auto one = [](size_t x) { return std::max(x, (size_t)1); };
+    // the graph as the kernel reads it: keyframe kf's list in row kf of a table of stride max(n_ordered, 1)
+    const size_t stride = one(NC);
+    std::vector<int32_t> ord((size_t)(kf + 1) * stride, -1), n_ord(K, 0);
+    std::copy(ordered, ordered + NC, ord.begin() + (size_t)kf * stride);
+    n_ord[kf] = n_ordered;
+    const spslam_cull_problem P{0, 0, kf, n_kf, 0, {0, 0, 0}};
+    enum { kMatchOff, kMatchRow, kObsOff, kObsKf, kObsKp, kSlot, kBad, kPoints, kOrdered, kNOrdered, kKeys, kURight,
+           kDepth, kNewPlane, kNotErase, kProblem, kRecords, kSummary };
+    Stage st(c);
+    if (int rc = st.open({{m.match_off, (K + 1) * 4}, {m.match_row, NM * 4, one(NM) * 4}, {m.obs_off, (R + 1) * 4},
+                           {m.obs_kf, NO * 4, one(NO) * 4}, {m.obs_kp, NO * 4, one(NO) * 4}, {m.kf_slot, K * 4},
+                           {m.point_bad, m.point_bad ? R : 0, one(R)}, {m.points, R * Pt, one(R) * Pt},
+                           {ord.data(), ord.size() * 4}, {n_ord.data(), K * 4}, {keys_un, S * Kp, one(S) * Kp},
+                           {uright, S * 4, one(S) * 4}, {depth, S * 4, one(S) * 4}, {new_plane, K},
+                           {not_erase, not_erase ? K : 0, K}, {&P, sizeof P}, one(NC) * sizeof(spslam_cull_record),
+                           sizeof(spslam_cull_summary)}))
+        return rc;
+    spslam_covis_map dm{};
+    dm.match_off = st.slot<int32_t>(kMatchOff);
+    dm.match_row = st.slot<int32_t>(kMatchRow);
+    dm.obs_off = st.slot<int32_t>(kObsOff);
+    dm.obs_kf = st.slot<int32_t>(kObsKf);
+    dm.obs_kp = st.slot<int32_t>(kObsKp);
+    dm.kf_slot = st.slot<int32_t>(kSlot);
+    dm.point_bad = m.point_bad ? st.slot<uint8_t>(kBad) : nullptr;
+    dm.points = st.slot<spslam_local_point>(kPoints);
+    spslam_covis_graph dg{};
+    dg.ordered = st.slot<int32_t>(kOrdered);
+    dg.n_ordered = st.slot<int32_t>(kNOrdered);
+    dg.stride = (int32_t)stride;
+    int rc = spslam_keyframe_culling_batch_device(
+        c, 1, st.slot<spslam_cull_problem>(kProblem), &dm, &dg, st.slot<spslam_keypoint>(kKeys),
+        st.slot<float>(kURight), st.slot<float>(kDepth), cap, st.slot<uint8_t>(kNewPlane),
+        not_erase ? st.slot<uint8_t>(kNotErase) : nullptr, params, st.slot<spslam_cull_record>(kRecords),
+        st.slot<spslam_cull_summary>(kSummary), c->stream);
+    if (rc) return rc;
+    HIP_CHECK(c, hipMemcpyAsync(summary, st.slot<void>(kSummary), sizeof *summary, hipMemcpyDeviceToHost, c->stream));
+    // the uploads read the vectors above, and the record count is the device's
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    if (summary->n_candidates > 0)
+        HIP_CHECK(c, hipMemcpyAsync(records, st.slot<void>(kRecords),
+                                    (size_t)summary->n_candidates * sizeof(spslam_cull_record), hipMemcpyDeviceToHost,
+                                    c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+int spslam_map_point_culling_batch_device(spslam_ctx* c, const spslam_point_cull_map* map, const int32_t* d_rows,
+                                          const int32_t* d_cur_kf_id, int n, int th_obs, uint8_t* d_verdict,
+                                          void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!map || n < 0 || (n && (!d_rows || !d_cur_kf_id || !d_verdict || !map->found || !map->visible ||
+                                !map->first_kf || !map->points)))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_map_point_culling_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    HIP_CHECK(c, map_point_culling_launch(*map, d_rows, d_cur_kf_id, n, th_obs, d_verdict, (hipStream_t)hip_stream));
+    return SPSLAM_OK;
+}
+
+int spslam_map_point_culling(spslam_ctx* c, const spslam_point_cull_map* map, int n_rows, const int32_t* rows, int n,
+                             int cur_kf_id, int th_obs, uint8_t* verdict) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!map || (n > 0 && !verdict) ||
+        (n_rows > 0 && (!map->found || !map->visible || !map->first_kf || !map->points)))
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_map_point_culling");
+    if (const char* e = covis_check_rows(rows, n, n_rows))
+        return fail(c, SPSLAM_ERR_ARG, "spslam_map_point_culling: %s", e);
+    if (n == 0) return SPSLAM_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const spslam_point_cull_map& m = *map;
+    const size_t R = (size_t)n_rows, N = (size_t)n, Pt = sizeof(spslam_local_point);
+    const std::vector<int32_t> ids(N, cur_kf_id);
+    enum { kFound, kVisible, kFirstKf, kBad, kPoints, kRows, kIds, kVerdict };
+    Stage st(c);
+    if (int rc = st.open({{m.found, R * 4}, {m.visible, R * 4}, {m.first_kf, R * 4},
+                           {m.point_bad, m.point_bad ? R : 0, R}, {m.points, R * Pt}, {rows, N * 4},
+                           {ids.data(), N * 4}, N}))
+        return rc;
+    spslam_point_cull_map dm{};
+    dm.found = st.slot<int32_t>(kFound);
+    dm.visible = st.slot<int32_t>(kVisible);
+    dm.first_kf = st.slot<int32_t>(kFirstKf);
+    dm.point_bad = m.point_bad ? st.slot<uint8_t>(kBad) : nullptr;
+    dm.points = st.slot<spslam_local_point>(kPoints);
+    int rc = spslam_map_point_culling_batch_device(c, &dm, st.slot<int32_t>(kRows), st.slot<int32_t>(kIds), n, th_obs,
+                                                   st.slot<uint8_t>(kVerdict), c->stream);
+    if (rc) return rc;
+    HIP_CHECK(c, hipMemcpyAsync(verdict, st.slot<void>(kVerdict), N, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));  // also: the uploads have read `ids`
     return SPSLAM_OK;
 }
 

@@ -357,3 +357,153 @@ class CreateNewPoints:
         self.ex._check(self.ex.lib.spslam_create_new_points_batch_device(
             self.ex.ctx, n_pairs, d_pairs, ctypes.byref(side), d_match12, d_nmatches, d_results, d_n_new,
             d_pair_status, stream or None))
+
+
+# ---------------------------------------------------------------- LocalMapping: covisibility graph, the cullings
+COVIS_MAX_KF, COVIS_BEST = 1024, 10
+COVIS_UPDATED, COVIS_EMPTY = 0, 1
+COVIS_TH = 15                              # KeyFrame::UpdateConnections' th
+CULL_KEPT, CULL_CULLED, CULL_DEFERRED, CULL_SKIPPED = range(4)
+CULL_RAN, CULL_NEW_PLANE = 0, 1
+POINT_CULL_KEEP, POINT_CULL_DROP, POINT_CULL_BAD_RATIO, POINT_CULL_BAD_OBS, POINT_CULL_EXPIRED = range(5)
+COVIS_PROBLEM_DTYPE = np.dtype([("kf_base", "<i4"), ("row_base", "<i4"), ("kf", "<i4"), ("n_kf", "<i4")])
+COVIS_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_ordered", "<i4"), ("new_parent", "<i4"), ("n_resorted", "<i4")])
+CULL_PROBLEM_DTYPE = np.dtype([("kf_base", "<i4"), ("row_base", "<i4"), ("kf", "<i4"), ("n_kf", "<i4"),
+                               ("out_offset", "<i4"), ("pad", "<i4", 3)])
+CULL_RECORD_DTYPE = np.dtype([("kf", "<i4"), ("n_mps", "<i4"), ("n_redundant", "<i4"), ("status", "<i4")])
+CULL_SUMMARY_DTYPE = np.dtype([("n_candidates", "<i4"), ("status", "<i4")])
+assert COVIS_PROBLEM_DTYPE.itemsize == 16 and COVIS_RESULT_DTYPE.itemsize == 16
+assert CULL_PROBLEM_DTYPE.itemsize == 32 and CULL_RECORD_DTYPE.itemsize == 16 and CULL_SUMMARY_DTYPE.itemsize == 8
+# the tables of spslam_covis_map, spslam_covis_graph (before `stride`) and spslam_point_cull_map, in their order
+COVIS_MAP_TABLES = (("match_off", np.int32), ("match_row", np.int32), ("obs_off", np.int32), ("obs_kf", np.int32),
+                    ("obs_kp", np.int32), ("kf_slot", np.int32), ("point_bad", np.uint8), ("points", LOCAL_POINT_DTYPE))
+COVIS_GRAPH_TABLES = (("weights", np.int32), ("ordered", np.int32), ("ordered_w", np.int32), ("n_ordered", np.int32),
+                      ("covis", np.int32), ("parent", np.int32), ("first_connection", np.uint8))
+POINT_CULL_TABLES = (("found", np.int32), ("visible", np.int32), ("first_kf", np.int32), ("point_bad", np.uint8),
+                     ("points", LOCAL_POINT_DTYPE))
+
+
+class CovisMap(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _ in COVIS_MAP_TABLES]
+
+
+class CovisGraph(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _ in COVIS_GRAPH_TABLES] + [("stride", ctypes.c_int32),
+                                                                             ("pad", ctypes.c_int32)]
+
+
+class CullParams(ctypes.Structure):
+    _fields_ = [("th_depth", ctypes.c_float), ("th_obs", ctypes.c_int32)]
+
+
+class PointCullMap(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _ in POINT_CULL_TABLES]
+
+
+spslam_gpu.EXPORTED += ["spslam_covis_update_connections", "spslam_covis_update_connections_batch_device",
+                        "spslam_keyframe_culling", "spslam_keyframe_culling_batch_device",
+                        "spslam_map_point_culling", "spslam_map_point_culling_batch_device"]
+
+
+def _bind_covis(lib):
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.spslam_covis_update_connections.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp]
+    lib.spslam_covis_update_connections_batch_device.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp]
+    lib.spslam_keyframe_culling.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.spslam_keyframe_culling_batch_device.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.spslam_map_point_culling.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp]
+    lib.spslam_map_point_culling_batch_device.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp]
+
+
+def _tables(tables, spec):
+    """The named arrays of a table spec, contiguous in their C types (None stays None)."""
+    return {name: None if tables.get(name) is None else np.ascontiguousarray(tables[name], dt).reshape(-1)
+            for name, dt in spec}
+
+
+class CovisUpdateConnections:
+    """GPU KeyFrame::UpdateConnections with AddConnection / UpdateBestCovisibles on the device-resident
+    spslam_covis_graph.  A call holds at most one problem per sequence; AddChild stays with the caller."""
+
+    def __init__(self, ex: spslam_gpu.OrbExtractor, th=COVIS_TH):
+        self.ex, self.th = ex, th
+        _bind_covis(ex.lib)
+
+    def __call__(self, tables, graph, stride, kf):
+        """One keyframe on host arrays: tables by COVIS_MAP_TABLES name (match / observer CSRs, point_bad), graph by
+        COVIS_GRAPH_TABLES name.  Returns (the graph after, as copies; the result record)."""
+        a = _tables(tables, COVIS_MAP_TABLES)
+        g = {name: np.array(graph[name], dt).reshape(-1) for name, dt in COVIS_GRAPH_TABLES}
+        res = np.zeros((), COVIS_RESULT_DTYPE)
+        m = CovisMap(**{name: _ptr(a[name]) for name, _ in COVIS_MAP_TABLES})
+        G = CovisGraph(stride=stride, **{name: _ptr(g[name]) for name, _ in COVIS_GRAPH_TABLES})
+        self.ex._check(self.ex.lib.spslam_covis_update_connections(
+            self.ex.ctx, ctypes.byref(m), len(a["match_off"]) - 1, len(a["obs_off"]) - 1, kf, self.th,
+            ctypes.byref(G), res.ctypes.data))
+        return g, res
+
+    def batch_device(self, n_problems, d_problems, covis_map: CovisMap, graph: CovisGraph, d_results, stream=0):
+        self.ex._check(self.ex.lib.spslam_covis_update_connections_batch_device(
+            self.ex.ctx, n_problems, d_problems, ctypes.byref(covis_map), ctypes.byref(graph), self.th, d_results,
+            stream or None))
+
+
+# LocalMapping::KeyFrameCulling: thObs = 3; mThDepth is the camera's (bf * ThDepth / fx)
+CULL_TH_OBS = 3
+
+
+class KeyFrameCulling:
+    """GPU LocalMapping::KeyFrameCulling (RGB-D): verdicts only, the caller applies SetBadFlag in order."""
+
+    def __init__(self, ex: spslam_gpu.OrbExtractor, th_depth, th_obs=CULL_TH_OBS):
+        self.ex = ex
+        _bind_covis(ex.lib)
+        self.params = CullParams(th_depth, th_obs)
+
+    def __call__(self, tables, kf, ordered, keys_un, uright, depth, cap, new_plane, not_erase=None):
+        """One current keyframe on host arrays.  Returns (records, summary)."""
+        a = _tables(tables, COVIS_MAP_TABLES)
+        k = np.ascontiguousarray(keys_un, spslam_gpu.KEYPOINT_DTYPE).reshape(-1)
+        ur = np.ascontiguousarray(uright, np.float32).reshape(-1)
+        dp = np.ascontiguousarray(depth, np.float32).reshape(-1)
+        assert len(k) % cap == 0 and len(ur) == len(k) == len(dp)
+        od = np.ascontiguousarray(ordered, np.int32)
+        npl = np.ascontiguousarray(new_plane, np.uint8)
+        ne = None if not_erase is None else np.ascontiguousarray(not_erase, np.uint8)
+        rec = np.zeros(max(len(od), 1), CULL_RECORD_DTYPE)
+        summary = np.zeros((), CULL_SUMMARY_DTYPE)
+        m = CovisMap(**{name: _ptr(a[name]) for name, _ in COVIS_MAP_TABLES})
+        self.ex._check(self.ex.lib.spslam_keyframe_culling(
+            self.ex.ctx, ctypes.byref(m), len(a["match_off"]) - 1, len(a["obs_off"]) - 1, kf, _ptr(od), len(od),
+            _ptr(k), _ptr(ur), _ptr(dp), cap, len(k) // cap, _ptr(npl), _ptr(ne), ctypes.byref(self.params),
+            rec.ctypes.data, summary.ctypes.data))
+        return rec[:int(summary["n_candidates"])], summary
+
+    def batch_device(self, n_problems, d_problems, covis_map: CovisMap, graph: CovisGraph, d_keys_un, d_uright,
+                     d_depth, cap, d_new_plane, d_not_erase, d_records, d_summaries, stream=0):
+        self.ex._check(self.ex.lib.spslam_keyframe_culling_batch_device(
+            self.ex.ctx, n_problems, d_problems, ctypes.byref(covis_map), ctypes.byref(graph), d_keys_un, d_uright,
+            d_depth, cap, d_new_plane, d_not_erase or None, ctypes.byref(self.params), d_records, d_summaries,
+            stream or None))
+
+
+class MapPointCulling:
+    """GPU LocalMapping::MapPointCulling: one POINT_CULL_* verdict per list entry."""
+
+    def __init__(self, ex: spslam_gpu.OrbExtractor, th_obs=CULL_TH_OBS):
+        self.ex, self.th_obs = ex, th_obs
+        _bind_covis(ex.lib)
+
+    def __call__(self, tables, rows, cur_kf_id):
+        a = _tables(tables, POINT_CULL_TABLES)
+        rw = np.ascontiguousarray(rows, np.int32)
+        verdict = np.full(max(len(rw), 1), 0xEE, np.uint8)
+        m = PointCullMap(**{name: _ptr(a[name]) for name, _ in POINT_CULL_TABLES})
+        self.ex._check(self.ex.lib.spslam_map_point_culling(self.ex.ctx, ctypes.byref(m), len(a["points"]), _ptr(rw),
+                                                            len(rw), cur_kf_id, self.th_obs, verdict.ctypes.data))
+        return verdict[:len(rw)]
+
+    def batch_device(self, point_map: PointCullMap, d_rows, d_cur_kf_id, n, d_verdict, stream=0):
+        self.ex._check(self.ex.lib.spslam_map_point_culling_batch_device(
+            self.ex.ctx, ctypes.byref(point_map), d_rows or None, d_cur_kf_id or None, n, self.th_obs,
+            d_verdict or None, stream or None))
