@@ -2,15 +2,19 @@
 // (src/Frame.cc:854-936) and the PCL 1.8 routines it calls.
 //
 //   plane_cloud_kernel     organized cloud, stride Cloud.Dis (Frame.cc:857-874)
+//   depth-change map + PCL's two-pass chamfer distance transform, as two
+//   anti-diagonal wavefronts (one lane per cloud row, slope 2): every cell
+//   sees exactly the operands of the reference's raster scan; PCL
+//   IntegralImage2D<float,3> of the x/y gradient images (fp64, same recurrence
+//   order) rides along in the first wavefront.  One of:
+//   plane_wave_kernel      one workgroup per frame, no workgroup barrier
+//                          (batches past 16 frames)
+//   plane_wave_roles_kernel
+//                          the same schedule in three workgroups per frame,
+//                          one per output group (up to 16 frames)
 //   plane_dist_integral_kernel
-//                          depth-change map + PCL's two-pass chamfer distance
-//                          transform, as two anti-diagonal wavefronts (one
-//                          lane per cloud row, slope 2): every cell sees
-//                          exactly the operands of the reference's raster scan
-//                          (made from the raster cloud through per-row LDS
-//                          windows); PCL IntegralImage2D<float,3> of the x/y
-//                          gradient images (fp64, same recurrence order) rides
-//                          along in the first wavefront
+//                          the barrier schedule on per-row LDS windows
+//                          (SPSLAM_PLANE_WAVE_BARRIER=1)
 //   plane_normal_kernel    AVERAGE_3D_GRADIENT normals + flip to viewpoint,
 //                          plane_d = p . n (one thread per cloud point)
 //   plane_segment_kernel   (plane_segment.hip) connected components, models,
@@ -887,6 +891,16 @@ hipError_t plane_launch_shape(const PlaneGeom& g, int n, spslam_plane_launch_sha
     return hipSuccess;
 }
 
+// The wave kernel of nw waves: one workgroup per frame, or three.
+using WaveKernel = decltype(&plane_wave_kernel<1>);
+template <int NWV>
+static WaveKernel wave_instance(bool one) { return one ? plane_wave_kernel<NWV> : plane_wave_roles_kernel<NWV>; }
+static WaveKernel wave_kernel(int nw, bool one) {
+    return nw <= 1 ? wave_instance<1>(one) : nw <= 2 ? wave_instance<2>(one) : nw <= 3 ? wave_instance<3>(one)
+         : nw <= 4 ? wave_instance<4>(one) : nw <= 5 ? wave_instance<5>(one) : nw <= 6 ? wave_instance<6>(one)
+         : nw <= 7 ? wave_instance<7>(one) : wave_instance<8>(one);
+}
+
 hipError_t plane_launch(const PlaneGeom& g, const PlaneBuffers& b, int n, const float* depth, long long depth_fs,
                         int depth_stride, spslam_plane* planes, int* plane_counts, int planes_cap, int32_t* inliers,
                         int32_t* contours, hipStream_t s, KernelTimer* timer, bool have_cloud) {
@@ -904,19 +918,10 @@ hipError_t plane_launch(const PlaneGeom& g, const PlaneBuffers& b, int n, const 
     B(kKindPlaneDist);
     const int nw = sh.wave_count;
     const size_t lds = (size_t)nw * 6 * g.W * sizeof(float);
-    if (!sh.barrier_rows && !sh.one_workgroup) {
-        auto* k = nw <= 1 ? plane_wave_roles_kernel<1> : nw <= 2 ? plane_wave_roles_kernel<2>
-                : nw <= 3 ? plane_wave_roles_kernel<3> : nw <= 4 ? plane_wave_roles_kernel<4>
-                : nw <= 5 ? plane_wave_roles_kernel<5> : nw <= 6 ? plane_wave_roles_kernel<6>
-                : nw <= 7 ? plane_wave_roles_kernel<7> : plane_wave_roles_kernel<8>;
-        hipLaunchKernelGGL(k, dim3(n, 3), dim3(64 * nw), lds, s, g, depth, depth_fs, depth_stride, b.wave, b.wave_fs,
-                           b.dist, b.dist_fs, b.integral, b.integral_fs);
-    } else if (!sh.barrier_rows) {
-        auto* k = nw <= 1 ? plane_wave_kernel<1> : nw <= 2 ? plane_wave_kernel<2> : nw <= 3 ? plane_wave_kernel<3>
-                : nw <= 4 ? plane_wave_kernel<4> : nw <= 5 ? plane_wave_kernel<5> : nw <= 6 ? plane_wave_kernel<6>
-                : nw <= 7 ? plane_wave_kernel<7> : plane_wave_kernel<8>;
-        hipLaunchKernelGGL(k, dim3(n), dim3(64 * nw), lds, s, g, depth, depth_fs, depth_stride, b.wave, b.wave_fs,
-                           b.dist, b.dist_fs, b.integral, b.integral_fs);
+    if (!sh.barrier_rows) {
+        hipLaunchKernelGGL(wave_kernel(nw, sh.one_workgroup), dim3(n, sh.one_workgroup ? 1 : 3), dim3(64 * nw), lds, s,
+                           g, depth, depth_fs, depth_stride, b.wave, b.wave_fs, b.dist, b.dist_fs, b.integral,
+                           b.integral_fs);
     } else {
         const int rows = wave_pitch(g.H);
         auto* k = sh.barrier_rows == 192   ? plane_dist_integral_kernel<192, kWaveChunk>

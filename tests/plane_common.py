@@ -201,6 +201,7 @@ GEOMETRY_CASES = {
     "h65": case(_c640(220, 208, 200, 65), 1, 200, True, 4, 2, 1, 1),                             # 200 x 65
     "h128": case(_c640(245, 176, 150, 128), 1, 200, True, 4, 2, 1, 1),                           # 150 x 128
     "h129": case(_c640(245, 176, 150, 129), 1, 200, True, 4, 3, 1, 1),                           # 150 x 129
+    "h330": case(_c640(245, 0, 150, 330), 1, 200, False, 4, 6, 2, 2),                            # 150 x 330
     "h65_indivisible": case(_c640(120, 143, 400, 193), 3, 200, True, 4, 2, 1, 1),                # 134 x 65
     "tall_100x512": case(_transposed(64, 200, 512, 100), 1, 300, False, 4, 8, 2, 3),             # 100 x 512
     "tall_96x480": case(_c640(272, 0, 96, 480), 1, 300, False, 4, 8, 2, 2),                      # 96 x 480
@@ -283,12 +284,14 @@ def batch_nonfinite(frames):
     return ([f for f, d in enumerate(frames) if np.isnan(d).any()], [f for f, d in enumerate(frames) if np.isposinf(d).any()])
 
 
-# Opt-in launch shapes: H <= 192, 192 < H <= 320 and H > 320 (plane_dist_integral_kernel's three instances).
+# Opt-in launch shapes: H <= 192, 192 < H <= 320 and H > 320 (plane_dist_integral_kernel's three instances), and for
+# the wave kernels' one- and three-workgroup shapes NW 1 (h64: no ring above or below) and NW 6 (h330: 10 rows in the
+# last wave).
 VARIANT_CASES = (("geometry", "h129"), ("geometry", "dis2"), ("geometry", "tall_96x480"),
                  ("nonfinite", "h129_nonfinite"), ("nonfinite", "dis2_nonfinite"),
-                 ("nonfinite", "tall_96x480_nonfinite"))
+                 ("nonfinite", "tall_96x480_nonfinite"), ("geometry", "h64"), ("geometry", "h330"))
 VARIANT_ROWS = {"h129": 192, "dis2": 320, "tall_96x480": 512, "h129_nonfinite": 192, "dis2_nonfinite": 320,
-                "tall_96x480_nonfinite": 512}
+                "tall_96x480_nonfinite": 512, "h64": 192, "h330": 512}
 VARIANTS = {"one_workgroup": {"SPSLAM_PLANE_WAVE": "1"}, "three_workgroups": {"SPSLAM_PLANE_WAVE": "3"},
             "barrier": {"SPSLAM_PLANE_WAVE_BARRIER": "1"}}
 

@@ -34,7 +34,7 @@ def test_cloud_sizes():
     assert sizes == {"wide_lds_300x100": (300, 100), "large_narrow_200x200": (200, 200),
                      "large_narrow_256x160": (256, 160), "w256": (256, 120), "w257": (257, 120), "w512": (512, 96),
                      "w63": (63, 100), "w64": (64, 100), "w65": (65, 100), "h64": (200, 64), "h65": (200, 65),
-                     "h128": (150, 128), "h129": (150, 129), "h65_indivisible": (134, 65),
+                     "h128": (150, 128), "h129": (150, 129), "h330": (150, 330), "h65_indivisible": (134, 65),
                      "tall_100x512": (100, 512), "tall_96x480": (96, 480), "dis2": (320, 240), "dis4": (160, 120),
                      "dis5": (128, 96), "patch_24x24": (24, 24)}
     d = PC.GEOMETRY_CASES["h65_indivisible"]["depth"]()
@@ -45,10 +45,10 @@ def test_cloud_sizes():
 
 def test_table_covers_every_launch():
     """What the cases pin (and the GPU tests assert through the launch-shape hook) covers all four segmentation
-    instances, K = 4 and 8 on each side of W = 256, and NW = 1, 2, 3, 4 and 8 (NW = 5: test_planes_c5_size)."""
+    instances, K = 4 and 8 on each side of W = 256, and NW = 1, 2, 3, 4, 6 and 8 (NW = 5: test_planes_c5_size)."""
     cases = list(PC.GEOMETRY_CASES.values())
     assert {(c["lds"], c["k"]) for c in cases} == {(True, 4), (True, 8), (False, 4), (False, 8)}
-    assert {c["nw"] for c in cases} == {1, 2, 3, 4, 8}
+    assert {c["nw"] for c in cases} == {1, 2, 3, 4, 6, 8}
     for c in cases:
         w, h = PC.cloud_size(c)
         assert c["k"] == (4 if w <= 256 else 8) and c["nw"] == -(-h // 64)
@@ -110,7 +110,16 @@ def test_variant_cases_cover_the_barrier_kernel():
     bound = {n: (192 if h <= 192 else 320 if h <= 320 else 512) for n, h in rows.items()}
     assert PC.VARIANT_ROWS == bound
     for table in ("geometry", "nonfinite"):
-        assert sorted(bound[n] for t, n in PC.VARIANT_CASES if t == table) == [192, 320, 512]
+        assert {bound[n] for t, n in PC.VARIANT_CASES if t == table} == {192, 320, 512}
+    assert sorted(bound[n] for t, n in PC.VARIANT_CASES if t == "nonfinite") == [192, 320, 512]
+
+
+def test_variant_cases_cover_the_wave_kernels():
+    """The forced one- and three-workgroup launches run the wave kernels without a ring (NW 1), with rings on both
+    sides of a wave (NW 3 and more), at NW 6, and with a last wave that is not full (h330: 10 of 64 rows)."""
+    nw = {n: PC.TABLES[t][n]["nw"] for t, n in PC.VARIANT_CASES}
+    assert (nw["h64"], nw["h330"]) == (1, 6) and {1, 3, 4, 6, 8} <= set(nw.values())
+    assert PC.cloud_size(PC.GEOMETRY_CASES["h64"])[1] == 64 and PC.cloud_size(PC.GEOMETRY_CASES["h330"])[1] % 64 == 10
 
 
 @pytest.mark.parametrize("name", list(PC.NONFINITE_CASES))
