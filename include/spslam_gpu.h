@@ -1632,6 +1632,145 @@ int spslam_search_by_bow_batch_device(spslam_ctx* ctx, int n_pairs, const int32_
                                       const spslam_bow_params* params, int32_t* d_match, int* d_nmatches,
                                       void* hip_stream);
 
+/* ---------------------------------------------------------------- place recognition: KeyFrameDatabase
+ * KeyFrameDatabase::DetectRelocalizationCandidates (src/KeyFrameDatabase.cc:199-309), the first call of
+ * Tracking::Relocalization (src/Tracking.cc:1573-1734); KeyFrameDatabase::DetectLoopCandidates (:76-197) and the
+ * reference score that LoopClosing::DetectLoop computes before it (src/LoopClosing.cc:126-140).  The candidates
+ * they return are the keyframe slots of the pair list of spslam_search_by_bow_batch_device.  PnP, Sim3 and the
+ * consistency groups (LoopClosing.cc:154-220) are not here; add() and erase() stay with the caller: they flip
+ * in_db.
+ *
+ * Tables.  All device resident; keyframe indices are local to a sequence, keyframe k of a problem is entry
+ * kf_base + k, as in spslam_covis_problem.  The neighbours come from spslam_covis_graph: covis is
+ * GetBestCovisibilityKeyFrames(10), weights (non-zero) is GetConnectedKeyFrames, ordered / n_ordered is
+ * GetVectorCovisibleKeyFrames.
+ *
+ * The inverted file is not mirrored: in_db says which keyframes it holds, and the order of every word's list
+ * follows from that.  Every add() of the reference is made by LoopClosing::DetectLoop (LoopClosing.cc:118,148)
+ * on keyframes it takes from a FIFO that LocalMapping fills in mnId order; erase() removes one element of a
+ * list and keeps the order of the rest (KeyFrameDatabase.cc:48-67).  So each word's list is in ascending
+ * keyframe index among the keyframes with in_db set, and walking the query's words in ascending word id (a
+ * BowVector is a std::map) over such lists meets the keyframes in this order: by the position, in the query
+ * vector, of the first word they share with it, then by keyframe index.  That is the order of
+ * lKFsSharingWords, and every later list of the two functions is a subsequence of it.
+ *
+ * reloc_score / loop_score are KeyFrame::mRelocScore / mLoopScore.  They persist across calls, and the
+ * relocalization query reads values that earlier queries left (below).  The reference leaves them uninitialised
+ * (KeyFrame.cc:35); the caller zero-fills them when a keyframe is created: 0 is a chosen value, the reference
+ * has none.
+ *
+ * Not reproduced: the stamps mnRelocQuery / mnLoopQuery start at 0, so in the reference a query whose id is 0
+ * finds every keyframe "already seen" and returns nothing.  Here every query starts with no keyframe seen. */
+#define SPSLAM_PLACE_MAX_WORDS 8192  /* a query vector's length at most (the cap of the BoW transform) */
+#define SPSLAM_PLACE_OK 0
+#define SPSLAM_PLACE_EMPTY 1         /* lKFsSharingWords.empty() (:107, :224): only the result record is written */
+#define SPSLAM_PLACE_NONE_KEPT 2     /* loop query, lScoreAndMatch.empty() (:141): the scores stay written */
+
+typedef struct spslam_place_db {
+    const uint32_t* bow_words;  /* the layout spslam_bow_transform_batch_device writes: slot kf_base + k at */
+    const double* bow_values;   /*   (kf_base + k) * cap, words ascending and unique                        */
+    const int* n_bow;           /* per keyframe, 0 .. cap */
+    const uint8_t* in_db;       /* per keyframe: set by add(), cleared by erase() */
+    float* reloc_score;         /* per keyframe: mRelocScore, written for the keyframes a relocalization query scores */
+    float* loop_score;          /* per keyframe: mLoopScore, written for the keyframes a loop query scores */
+    int32_t cap;                /* 1 .. SPSLAM_PLACE_MAX_WORDS */
+    int32_t pad;
+} spslam_place_db;
+
+typedef struct spslam_place_frames {  /* the query frames' BowVectors, frame slot f at f * cap */
+    const uint32_t* bow_words;
+    const double* bow_values;
+    const int* n_bow;
+    int32_t cap;                /* 1 .. SPSLAM_PLACE_MAX_WORDS */
+    int32_t pad;
+} spslam_place_frames;
+
+typedef struct spslam_place_problem {
+    int32_t kf_base;
+    int32_t n_kf;               /* keyframes of this sequence, 1 .. SPSLAM_COVIS_MAX_KF */
+    int32_t query;              /* relocalization: the frame slot; loop and min-score entries: the keyframe index */
+    int32_t out_offset;         /* the problem's first candidate in d_candidates; room for n_kf entries */
+} spslam_place_problem;         /* 16 bytes */
+
+typedef struct spslam_place_result {
+    int32_t status;             /* SPSLAM_PLACE_* */
+    int32_t n_sharing;          /* lKFsSharingWords.size() */
+    int32_t max_common_words;
+    int32_t min_common_words;   /* (int)(max_common_words * 0.8f) */
+    int32_t n_scored;           /* nscores */
+    int32_t n_kept;             /* lScoreAndMatch.size(): relocalization n_scored, loop those with score >= min_score */
+    int32_t n_candidates;
+    float best_acc_score;       /* bestAccScore; EMPTY: 0, NONE_KEPT: min_score */
+} spslam_place_result;          /* 32 bytes; EMPTY: every field after n_sharing is 0 */
+
+/* The score of two BowVectors is L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68): the sum in
+ * double, over the shared words in ascending word id, of fabs(vi - wi) - fabs(vi) - fabs(wi) with vi the query's
+ * value; then -sum / 2.0 in double, rounded to float where the reference stores it in one.  The float has the
+ * bits of that serial sum.
+ *
+ * DetectRelocalizationCandidates for problem p's frame, one workgroup per problem:
+ *   sharing list (:207-225): every in_db keyframe with at least one word in common with the query, in the order
+ *     derived above; c_i its number of common words.  Empty: SPSLAM_PLACE_EMPTY, n_candidates 0, and neither a
+ *     score nor a candidate is written;
+ *   word threshold (:228-235): max_common_words = max c_i, min_common_words = (int)(max * 0.8f), the product in
+ *     float;
+ *   scores (:242-253): the keyframes with c_i > min_common_words, in list order; reloc_score[i] is written for
+ *     these only;
+ *   accumulation (:262-287): per scored keyframe, acc starts as its score (float) and best as the keyframe; its
+ *     covis row is walked in order (-1 skipped), and every neighbour that is in the sharing list of this query
+ *     adds its reloc_score to acc and takes over best on a strictly greater score.  A neighbour in the list that
+ *     this query did not score contributes reloc_score as stored: the value of the last query that scored it, or
+ *     the initial 0 (:273-281 test mnRelocQuery only).  best_acc_score is the maximum acc, from 0;
+ *   retention (:290-306): acc > 0.75f * best_acc_score; d_candidates + out_offset receives the best keyframes of
+ *     the kept entries in list order, each at its first occurrence only.  Entries past n_candidates are not
+ *     written.
+ * CONTRACT: a call holds at most one problem per sequence (the score tables are shared state).  Successive
+ * queries of one sequence are successive calls on one stream.  graph: only covis is read. */
+int spslam_place_reloc_candidates_batch_device(spslam_ctx* ctx, int n_problems,
+                                               const spslam_place_problem* d_problems, const spslam_place_db* db,
+                                               const spslam_place_frames* frames, const spslam_covis_graph* graph,
+                                               spslam_place_result* d_results, int32_t* d_candidates,
+                                               void* hip_stream);
+
+/* DetectLoopCandidates for problem p's keyframe `query`; the same walk with these differences:
+ *   the query vector is the keyframe's own.  CONTRACT: in_db[query] is 0 (DetectLoop adds it after the query,
+ *     LoopClosing.cc:148);
+ *   a keyframe i with weights[query][i] != 0 is connected (:78, :96): outside the sharing list and every later
+ *     step, also where it stands in a neighbour's covis row;
+ *   loop_score[i] is written for every scored keyframe (:135); those with score >= min_score become entries
+ *     (:136), n_kept of them.  None: SPSLAM_PLACE_NONE_KEPT, n_candidates 0;
+ *   a neighbour contributes to acc only if this query scored it: in the list and c > min_common_words (:159);
+ *   best_acc_score starts at min_score (:145);
+ *   min_score is d_min_score[p], a device float, so that spslam_place_min_score_batch_device chains into this
+ *     entry on one stream.
+ * graph: covis, weights and stride are read. */
+int spslam_place_loop_candidates_batch_device(spslam_ctx* ctx, int n_problems,
+                                              const spslam_place_problem* d_problems, const spslam_place_db* db,
+                                              const spslam_covis_graph* graph, const float* d_min_score,
+                                              spslam_place_result* d_results, int32_t* d_candidates,
+                                              void* hip_stream);
+
+/* LoopClosing.cc:126-140: d_min_score[p] = the minimum, in float from 1.0f, of score(query, j) over the
+ * keyframes j of query's ordered list that d_kf_bad (per keyframe, may be NULL: none) does not flag.  in_db is
+ * not read.  graph: ordered, n_ordered and stride are read; out_offset is not used. */
+int spslam_place_min_score_batch_device(spslam_ctx* ctx, int n_problems, const spslam_place_problem* d_problems,
+                                        const spslam_place_db* db, const spslam_covis_graph* graph,
+                                        const uint8_t* d_kf_bad, float* d_min_score, void* hip_stream);
+
+/* One problem on host arrays (db's and graph's pointers too) at base 0, n_kf keyframes.  Every index is checked
+ * (n_kf, cap, n_bow <= cap, ascending words, covis, ordered, query): SPSLAM_ERR_ARG on a violation, nothing
+ * launched.  db->reloc_score / db->loop_score are rewritten in place; candidates has room for n_kf entries and
+ * is written up to result->n_candidates.  The relocalization query is q_n words (<= SPSLAM_PLACE_MAX_WORDS).
+ * The loop form refuses in_db[query] != 0. */
+int spslam_place_reloc_candidates(spslam_ctx* ctx, const spslam_place_db* db, int n_kf, const uint32_t* q_words,
+                                  const double* q_values, int q_n, const spslam_covis_graph* graph,
+                                  spslam_place_result* result, int32_t* candidates);
+int spslam_place_loop_candidates(spslam_ctx* ctx, const spslam_place_db* db, int n_kf, int query,
+                                 const spslam_covis_graph* graph, float min_score, spslam_place_result* result,
+                                 int32_t* candidates);
+int spslam_place_min_score(spslam_ctx* ctx, const spslam_place_db* db, int n_kf, int query,
+                           const spslam_covis_graph* graph, const uint8_t* kf_bad, float* min_score);
+
 /* ---------------------------------------------------------------- the whole batched step
  * The throughput path as one call per step, for a C / C++ caller: GrabImageRGBD (Tracking.cc:208-229) ->
  * ORB extraction || ComputePlanesFromOrganizedPointCloud + GeneratePlanesFromBoundries (the RGB-D Frame
