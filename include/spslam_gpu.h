@@ -1771,6 +1771,155 @@ int spslam_place_loop_candidates(spslam_ctx* ctx, const spslam_place_db* db, int
 int spslam_place_min_score(spslam_ctx* ctx, const spslam_place_db* db, int n_kf, int query,
                            const spslam_covis_graph* graph, const uint8_t* kf_bad, float* min_score);
 
+/* ---------------------------------------------------------------- LoopClosing: ComputeSim3 and SearchAndFuse
+ * The four ORBmatcher overloads LoopClosing calls after DetectLoop (src/LoopClosing.cc:233-432, :674-715), on the
+ * tables the library keeps in HBM: the frame stage's keyframe slots, the FeatureVector CSR of
+ * spslam_bow_transform_batch_device, the spslam_local_point table and the match_off / match_row CSR.
+ *   SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12)              src/ORBmatcher.cc:522-655   (LoopClosing.cc:267)
+ *   SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)    src/ORBmatcher.cc:1102-1326 (LoopClosing.cc:325)
+ *   SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)       src/ORBmatcher.cc:290-403   (LoopClosing.cc:393)
+ *   Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)                src/ORBmatcher.cc:977-1100  (LoopClosing.cc:700)
+ * All four are deterministic.  Sim3Solver, OptimizeSim3, the consistency groups and CorrectLoop's map mutation stay
+ * with the caller.  None of these entries has a timing kind, and none is part of the batched step.
+ * KeyFrame's image bounds are ints (include/KeyFrame.h:198-201): the configured bounds are truncated, as for
+ * spslam_fuse_search.  The host-pointer forms take one problem and check every index before anything is launched
+ * (SPSLAM_ERR_ARG on a violation). */
+
+/* ---- SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12).  Both sides are spslam_bow_side with keys = mvKeysUn and
+ * has_point[i] = GetMapPointMatches()[i] && !isBad(), read on both sides.  Pair p = (slot 1, slot 2) =
+ * d_pairs[2p], d_pairs[2p+1]; d_match12 at p * kf1->cap holds, per KF1 keypoint, the KF2 keypoint index or -1 (the
+ * caller maps it through vpMapPoints2), written for the slot's counts[slot 1] keypoints; d_nmatches one int per
+ * pair.  Unlike the keyframe-to-frame overload acceptance is bestDist1 < TH_LOW, strict (:598), the result and the
+ * rotation histogram are indexed by idx1, and a KF2 keypoint stays blocked (vbMatched2) for a match that the
+ * histogram later removes.  kf1->cap * 13 + kf2->cap bytes of LDS: <= 150 KB. */
+int spslam_search_by_bow_kf_batch_device(spslam_ctx* ctx, int n_pairs, const int32_t* d_pairs,
+                                         const spslam_bow_side* kf1, const spslam_bow_side* kf2,
+                                         const spslam_bow_params* params, int32_t* d_match12, int* d_nmatches,
+                                         void* hip_stream);
+
+/* One keyframe of the host form: n keypoints, its FeatureVector as spslam_bow_transform returns it. */
+typedef struct spslam_bow_keyframe {
+    const uint8_t* desc;             /* n * 32 */
+    const spslam_keypoint* keys_un;  /* n (only .angle is read) */
+    const uint8_t* has_point;        /* n */
+    const uint32_t* fv_nodes;        /* n_fv, strictly ascending */
+    const int32_t* fv_start;         /* n_fv + 1, from 0, not descending, fv_start[n_fv] <= n */
+    const int32_t* fv_features;      /* fv_start[n_fv] entries in [0, n) */
+    int32_t n, n_fv;
+} spslam_bow_keyframe;
+
+/* Drop-in for one pair on host buffers.  match12: kf1->n ints. */
+int spslam_search_by_bow_kf(spslam_ctx* ctx, const spslam_bow_keyframe* kf1, const spslam_bow_keyframe* kf2,
+                            const spslam_bow_params* params, int32_t* match12, int* nmatches);
+
+/* ---- SearchBySim3.  The map, as spslam_covis_map / spslam_point_refresh_map point at it: keyframe k has pose
+ * kf_Tcw + 16k and its arrays in slot kf_slot[k] of the frame stage's layouts; its GetMapPointMatches are
+ * match_row[match_off[k] + i] for keypoint i (the point's row in `points`, or -1), counts[slot] of them. */
+typedef struct spslam_sim3_map {
+    const float* kf_Tcw;        /* n_kf * 16, row-major: GetRotation / GetTranslation */
+    const int32_t* kf_slot;     /* n_kf */
+    const int32_t* match_off;   /* n_kf + 1, absolute offsets into match_row */
+    const int32_t* match_row;
+    const uint8_t* point_bad;   /* per row, may be NULL: none */
+    const spslam_local_point* points;
+} spslam_sim3_map;
+
+/* One call of SearchBySim3.  sR12 = s12*R12, sR21 = (1.0/s12)*R12.t() and t21 = -sR21*t12 (:1119-1121) are made on
+ * the device from s12, R12 and t12, so that their bits are the library's and not the binding's. */
+typedef struct spslam_sim3_pair {
+    int32_t kf1, kf2;         /* keyframe indices of the map */
+    int32_t match_offset;     /* vpMatches12, in and out: N1 ints at d_match12 + match_offset, KF2 keypoint or -1 */
+    int32_t result_offset;    /* n_found at d_n_found[result_offset] */
+    float s12;
+    float R12[9];             /* row-major */
+    float t12[3];
+    int32_t pad[3];
+} spslam_sim3_pair;           /* 80 bytes */
+
+typedef struct spslam_sim3_params {
+    float th;                 /* radius at level 0 (7.5 in ComputeSim3) */
+    int32_t pad;
+} spslam_sim3_params;
+
+/* Batched, device resident.  On entry vbAlreadyMatched1[i] is match12[i] >= 0 and vbAlreadyMatched2[match12[i]] is
+ * set for the same entries: the reference's GetIndexInKeyFrame(pKF2) (:1138) whenever the map is consistent, that
+ * is, whenever the point that vpMatches12[i] names is observed by pKF2 at the keypoint the caller derived it from.
+ * A binding that cannot promise that passes d_already2 (may be NULL): one byte per KF2 keypoint, pair p's at
+ * p * cap, which then replaces the derived flags of every pair of the call.  The two searches (:1148-1305) run in one launch and do
+ * not depend on order; a second launch does the agreement pass (:1307-1323), which writes match12[i1] = idx2 for
+ * the pairs found and leaves every other entry as it was.  Pairs' match12 ranges must be disjoint.  cap: keypoint
+ * slots per keyframe slot; the call keeps 9 * cap bytes of scratch per pair in the context, which
+ * spslam_search_by_projection_sim3_batch_device uses too: calls that share a context are ordered on one stream. */
+int spslam_search_by_sim3_batch_device(spslam_ctx* ctx, int n_pairs, const spslam_sim3_pair* d_pairs,
+                                       const spslam_sim3_map* map, const spslam_keypoint* d_keys_un,
+                                       const uint8_t* d_desc, const int32_t* d_grid_off, const int32_t* d_grid_idx,
+                                       const int* d_counts, int cap, const uint8_t* d_already2,
+                                       const spslam_sim3_params* params, int32_t* d_match12, int* d_n_found,
+                                       void* hip_stream);
+
+/* One keyframe of the host form. */
+typedef struct spslam_sim3_keyframe {
+    const float* Tcw;                /* 16 */
+    const spslam_keypoint* keys_un;  /* n */
+    const uint8_t* desc;             /* n * 32 */
+    const int32_t* grid_off;         /* 64*48 + 1: from 0, not descending, grid_off[64*48] <= n */
+    const int32_t* grid_idx;         /* grid_off[64*48] entries in [0, n) */
+    const int32_t* match_row;        /* n entries in [-1, n_rows) */
+    int32_t n, pad;
+} spslam_sim3_keyframe;
+
+/* Drop-in for one pair on host buffers: points / point_bad (may be NULL) are n_rows table rows; match12 (kf1->n
+ * ints in [-1, kf2->n)) is rewritten in place; already2: kf2->n bytes or NULL.  *n_found receives the return
+ * value.  pair->kf1 / kf2 / offsets are ignored. */
+int spslam_search_by_sim3(spslam_ctx* ctx, const spslam_sim3_keyframe* kf1, const spslam_sim3_keyframe* kf2,
+                          const spslam_local_point* points, const uint8_t* point_bad, int n_rows,
+                          const spslam_sim3_pair* pair, const uint8_t* already2, const spslam_sim3_params* params,
+                          int32_t* match12, int* n_found);
+
+/* ---- SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) and the search of Fuse(pKF, Scw, vpPoints, th,
+ * vpReplacePoint).  Both take spslam_fuse_problem records whose Tcw field holds Scw; the decomposition (:298-303,
+ * :985-990: scw, Rcw = sRcw/scw, tcw = col3/scw, Ow) is made on the device.  The keyframe's uright is not read. */
+
+/* Fuse with Scw: the same records, statuses and nfused = the count of best_dist <= TH_LOW as spslam_fuse_search,
+ * without the chi-square test.  d_skip[out index] is the caller's flag isBad() || spAlreadyFound.count(pMP)
+ * (:1005) as it was on entry; the search never reads GetMapPoint, so one call is a pure search over a snapshot,
+ * and the walk :1082-1096 (vpReplacePoint[iMP] or AddObservation / AddMapPoint; a bad pMPinKF is counted with
+ * nothing done) stays with the caller.  CONTRACT, as Fuse's: a point occurs at most once in a problem's list. */
+int spslam_fuse_sim3_search_batch_device(spslam_ctx* ctx, int n_problems, const spslam_fuse_problem* d_problems,
+                                         const spslam_local_point* d_points, int max_points,
+                                         const spslam_keypoint* d_keys_un, const uint8_t* d_desc,
+                                         const int32_t* d_grid_off, const int32_t* d_grid_idx, const int* d_counts,
+                                         int cap, const uint8_t* d_skip, const spslam_fuse_params* params,
+                                         spslam_fuse_result* d_results, int* d_nfused, void* hip_stream);
+int spslam_fuse_sim3_search(spslam_ctx* ctx, const float* Scw, const spslam_local_point* points, int n_points,
+                            const spslam_keypoint* keys_un, const uint8_t* desc, int n_kp, const int32_t* grid_off,
+                            const int32_t* grid_idx, const uint8_t* skip, const spslam_fuse_params* params,
+                            spslam_fuse_result* results, int* nfused);
+
+/* SearchByProjection with Scw.  d_skip[out index]: isBad() || in spAlreadyFound (:317).  d_taken at problem *
+ * cap (may be NULL: none): vpMatched[idx] != NULL on entry, per keyframe keypoint.  d_match at problem * cap, for
+ * the keyframe's counts[kf_slot] keypoints: the index (in the problem's list) of the point newly assigned to the
+ * keypoint, else -1; d_nmatches one int per problem.  The search of point i skips the keypoints that the points
+ * before it took (:375, :396): a window kernel keeps each point's SPSLAM_PROJ_SIM3_KEYS smallest candidates among
+ * the keypoints not taken on entry, and one wave per problem walks the points in order.  CONTRACT, as Fuse's: a
+ * point occurs at most once in a problem's list (mnLoopPointForKF guarantees it in the reference).  params->th is
+ * the reference's int th (10 in ComputeSim3) as a float.  cap <= 36000 (the walk's LDS). */
+#define SPSLAM_PROJ_SIM3_KEYS 4
+int spslam_search_by_projection_sim3_batch_device(spslam_ctx* ctx, int n_problems,
+                                                  const spslam_fuse_problem* d_problems,
+                                                  const spslam_local_point* d_points, int max_points,
+                                                  const spslam_keypoint* d_keys_un, const uint8_t* d_desc,
+                                                  const int32_t* d_grid_off, const int32_t* d_grid_idx,
+                                                  const int* d_counts, int cap, const uint8_t* d_skip,
+                                                  const uint8_t* d_taken, const spslam_fuse_params* params,
+                                                  int32_t* d_match, int* d_nmatches, void* hip_stream);
+/* taken: n_kp bytes or NULL; match: n_kp ints. */
+int spslam_search_by_projection_sim3(spslam_ctx* ctx, const float* Scw, const spslam_local_point* points,
+                                     int n_points, const spslam_keypoint* keys_un, const uint8_t* desc, int n_kp,
+                                     const int32_t* grid_off, const int32_t* grid_idx, const uint8_t* skip,
+                                     const uint8_t* taken, const spslam_fuse_params* params, int32_t* match,
+                                     int* nmatches);
+
 /* ---------------------------------------------------------------- the whole batched step
  * The throughput path as one call per step, for a C / C++ caller: GrabImageRGBD (Tracking.cc:208-229) ->
  * ORB extraction || ComputePlanesFromOrganizedPointCloud + GeneratePlanesFromBoundries (the RGB-D Frame

@@ -22,6 +22,8 @@
 //                       64 lanes split the node's frame features, reducing (best, first
 //                       index, second best) exactly as the sequential `<` scan; rotation
 //                       histogram + ComputeThreeMaxima at the end.
+//   bow_search_kf_kernel  ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (src/ORBmatcher.cc:522-655),
+//                       the same shape, described at the kernel.
 //   triangulation_search_kernel  ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:657-823), described at
 //                       the kernel.
 // Integer / index work and fp64 sums in the reference's order: bit-exact.
@@ -341,6 +343,99 @@ __global__ __launch_bounds__(kThreads) void bow_search_kernel(const int2* __rest
     if (t == 0) nmatches_out[p] = n_total - n_removed;
 }
 
+// ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (src/ORBmatcher.cc:522-655), bow_search_kernel's shape:
+// workgroup per (keyframe 1, keyframe 2) pair, the shared nodes listed in LDS, a wave per node, the node's idx1 in
+// list order (vbMatched2 makes them order dependent; a feature sits in one node, so nodes are independent) and the
+// 64 lanes over the node's idx2.  What differs from the keyframe-to-frame overload: has_point is read on both sides,
+// acceptance is bestDist1 < TH_LOW (:598), the result, the histogram and the bins are indexed by idx1, and vbMatched2
+// is a table of its own that a match removed by the histogram leaves set.
+__global__ __launch_bounds__(kThreads) void bow_search_kf_kernel(const int2* __restrict__ pairs, BowSide A, BowSide B,
+                                                                 float nn_ratio, int check_ori,
+                                                                 int32_t* __restrict__ match_out,
+                                                                 int* __restrict__ nmatches_out) {
+    extern __shared__ int smem[];
+    int2* shared_nodes = reinterpret_cast<int2*>(smem);                       // [A.cap]
+    int32_t* match = smem + 2 * A.cap;                                        // [A.cap] by idx1
+    signed char* bin = reinterpret_cast<signed char*>(match + A.cap);         // [A.cap] by idx1
+    uint8_t* matched2 = reinterpret_cast<uint8_t*>(bin + A.cap);              // [B.cap] vbMatched2
+    __shared__ int hist[kHisto];
+    __shared__ int n_shared, n_total, n_removed;
+    __shared__ int ind[3];
+    const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int k1 = pairs[p].x, k2 = pairs[p].y;
+    const int n1 = min(A.counts[k1], A.cap), n2 = min(B.counts[k2], B.cap);
+    for (int i = t; i < A.cap; i += kThreads) {
+        match[i] = -1;
+        bin[i] = -1;
+    }
+    for (int i = t; i < B.cap; i += kThreads) matched2[i] = 0;
+    if (t < kHisto) hist[t] = 0;
+    if (t == 0) { n_shared = 0; n_total = 0; n_removed = 0; }
+    __syncthreads();
+    const uint32_t* nodes1 = A.fv_nodes + (size_t)k1 * A.cap;
+    const uint32_t* nodes2 = B.fv_nodes + (size_t)k2 * B.cap;
+    const int nfv1 = min(A.n_fv[k1], A.cap), nfv2 = min(B.n_fv[k2], B.cap);
+    for (int a = t; a < nfv1; a += kThreads) {
+        const int l = find_node(nodes2, nfv2, nodes1[a]);
+        if (l >= 0) shared_nodes[atomicAdd(&n_shared, 1)] = make_int2(a, l);
+    }
+    __syncthreads();
+    const int32_t* fs1 = A.fv_start + (size_t)k1 * (A.cap + 1);
+    const int32_t* fs2 = B.fv_start + (size_t)k2 * (B.cap + 1);
+    const int32_t* feat1 = A.fv_features + (size_t)k1 * A.cap;
+    const int32_t* feat2 = B.fv_features + (size_t)k2 * B.cap;
+    const uint4* desc1 = reinterpret_cast<const uint4*>(A.desc + (size_t)k1 * A.cap * 32);
+    const uint4* desc2 = reinterpret_cast<const uint4*>(B.desc + (size_t)k2 * B.cap * 32);
+    const uint8_t* has1 = A.has_point + (size_t)k1 * A.cap;
+    const uint8_t* has2 = B.has_point + (size_t)k2 * B.cap;
+    const spslam_keypoint* kun1 = A.keys + (size_t)k1 * A.cap;
+    const spslam_keypoint* kun2 = B.keys + (size_t)k2 * B.cap;
+    int count = 0;
+    for (int s = wave; s < n_shared; s += kThreads / 64) {
+        const int2 nd = shared_nodes[s];
+        const int f0 = max(fs2[nd.y], 0), f1 = min(fs2[nd.y + 1], B.cap);
+        const int q1 = min(fs1[nd.x + 1], A.cap);
+        for (int q = max(fs1[nd.x], 0); q < q1; q++) {
+            const int idx1 = feat1[q];
+            if ((unsigned)idx1 >= (unsigned)n1 || !has1[idx1]) continue;          // :558-562
+            const uint4 a0 = desc1[2 * idx1], a1 = desc1[2 * idx1 + 1];
+            Best b{256, 1 << 30, 256};
+            for (int r = f0 + lane; r < f1; r += 64) {
+                const int idx2 = feat2[r];
+                if ((unsigned)idx2 >= (unsigned)n2 || matched2[idx2] || !has2[idx2]) continue;   // :576-580
+                const int d = hamming(a0, a1, desc2[2 * idx2], desc2[2 * idx2 + 1]);
+                if (d < b.b1) { b.b2 = b.b1; b.b1 = d; b.i1 = r; }
+                else if (d < b.b2) b.b2 = d;
+            }
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                Best x{__shfl_xor(b.b1, o), __shfl_xor(b.i1, o), __shfl_xor(b.b2, o)};
+                b = merge(b, x);
+            }
+            if (b.b1 < kThLow && (float)b.b1 < __fmul_rn(nn_ratio, (float)b.b2)) {  // :598, strict
+                const int idx2 = feat2[b.i1];
+                const int bn = check_ori ? rotation_bin(kun1[idx1].angle, kun2[idx2].angle) : 0;
+                if (lane == 0) {
+                    match[idx1] = idx2;
+                    matched2[idx2] = 1;
+                    if (check_ori && (unsigned)bn < (unsigned)kHisto) {  // the reference asserts it
+                        bin[idx1] = (signed char)bn;
+                        atomicAdd(&hist[bn], 1);
+                    }
+                }
+                count++;
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    if (lane == 0 && count) atomicAdd(&n_total, count);
+    __syncthreads();
+    if (check_ori) keep_three_maxima(hist, ind, bin, match, n1, &n_removed);
+    int32_t* mo = match_out + (size_t)p * A.cap;
+    for (int i = t; i < n1; i += kThreads) mo[i] = match[i];
+    if (t == 0) nmatches_out[p] = n_total - n_removed;
+}
+
 // ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:657-823, CheckDistEpipolarLine :140-157), workgroup per
 // (current keyframe, neighbour) pair.  vbMatched2 is never written in the reference, so every key-1 feature without
 // a map point is an independent item: the items of the shared nodes are listed in LDS (any order), and a group of
@@ -530,6 +625,19 @@ hipError_t bow_search_launch(int n_pairs, const int2* pairs, const BowSide& kf, 
     hipLaunchKernelGGL(bow::bow_search_kernel, dim3(n_pairs), dim3(bow::kThreads), (lds + 15) / 16 * 16, s, pairs, kf,
                        fr, nn_ratio, check_ori, match, nmatches);
     if (timer) timer->end(kKindBowMatch, s);
+    return hipGetLastError();
+}
+
+hipError_t bow_search_kf_launch(int n_pairs, const int2* pairs, const BowSide& kf1, const BowSide& kf2, float nn_ratio,
+                                int check_ori, int32_t* match12, int* nmatches, hipStream_t s) {
+    if (n_pairs < 1 || kf1.cap < 1 || kf2.cap < 1) return hipErrorInvalidValue;
+    const size_t lds = (size_t)kf1.cap * 13 + (size_t)kf2.cap;  // match, shared nodes, bins; vbMatched2
+    if (lds > 150 * 1024) return hipErrorInvalidValue;
+    static const hipError_t lds_attr = hipFuncSetAttribute((const void*)bow::bow_search_kf_kernel,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (lds_attr != hipSuccess) return lds_attr;
+    hipLaunchKernelGGL(bow::bow_search_kf_kernel, dim3(n_pairs), dim3(bow::kThreads), (lds + 15) / 16 * 16, s, pairs,
+                       kf1, kf2, nn_ratio, check_ori, match12, nmatches);
     return hipGetLastError();
 }
 

@@ -56,6 +56,11 @@ struct BowSide {
 hipError_t bow_search_launch(int n_pairs, const int2* pairs, const BowSide& kf, const BowSide& fr, float nn_ratio,
                              int check_ori, int32_t* match, int* nmatches, hipStream_t s, KernelTimer* timer);
 
+// ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) per (slot 1, slot 2) pair: has_point is read on both
+// sides, keys are mvKeysUn on both; match12 at p * kf1.cap holds the KF2 keypoint or -1.  No timing kind.
+hipError_t bow_search_kf_launch(int n_pairs, const int2* pairs, const BowSide& kf1, const BowSide& kf2, float nn_ratio,
+                                int check_ori, int32_t* match12, int* nmatches, hipStream_t s);
+
 // Camera and level tables of the CreateNewMapPoints kernels (Frame.cc:118-124: invfx = 1.0f/fx, mb = mbf/fx;
 // ratio_factor = 1.5f*mfScaleFactor, LocalMapping.cc:245).
 struct TriConsts {

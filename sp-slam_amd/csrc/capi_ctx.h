@@ -205,6 +205,8 @@ struct spslam_ctx : CtxStreams {
     VocabDev vocab{};
     DevBuf<> d_bow_scratch;
     DevBuf<> d_bow_stage;
+    // loop closing: SearchByProjection(pKF, Scw)'s windows, SearchBySim3's vnMatch1 / vnMatch2 and flags
+    DevBuf<> d_loop_scratch;
 
     // Call with the context's device current.  The last LBA launch may still read its buffers on a caller stream.
     ~spslam_ctx() {
@@ -249,7 +251,7 @@ inline size_t stage_layout(const StageSlot* slots, int n, size_t* off) {
 // context's persistent buffers, which a need above its capacity grows to `grow` times that need.  open() and
 // close() return SPSLAM codes and leave the failing HIP call in the context's error string.
 struct Stage {
-    static constexpr int kMaxSlots = 18;
+    static constexpr int kMaxSlots = 20;
     spslam_ctx* c;
     uint8_t* q = nullptr;
     bool temporary = false;

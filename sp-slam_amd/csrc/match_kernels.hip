@@ -23,6 +23,9 @@
 //                        histogram check.
 //   fuse_search_kernel   ORBmatcher::Fuse(pKF, vpMapPoints, th), the search (:842-949): the window kernel's
 //                        shape, 4 lanes per point, with Fuse's own candidate test; no in-order walk (below).
+//   sim3_search_kernel, sim3_agree_kernel; proj_sim3_window_kernel, proj_sim3_assign_kernel;
+//   fuse_sim3_search_kernel   LoopClosing's Sim3 matchers: SearchBySim3 (:1102-1326), SearchByProjection(pKF, Scw,
+//                        ...) (:290-403) and the search of Fuse(pKF, Scw, ...) (:977-1079), described at the kernels.
 // Float expressions follow the reference build's contraction pattern; the
 // cv::Mat products are accumulated in double and rounded once (oracle header).
 #include <hip/hip_runtime.h>
@@ -855,6 +858,433 @@ __global__ __launch_bounds__(kThreads) void fuse_search_kernel(const spslam_fuse
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(&nfused[f], n);
 }
 
+// ---------------------------------------------------------------------------
+// LoopClosing's Sim3 matchers: SearchBySim3 (src/ORBmatcher.cc:1102-1326), SearchByProjection(pKF, Scw, ...)
+// (:290-403) and the search of Fuse(pKF, Scw, ...) (:977-1079).  One point per kLGrp lanes, as fuse_search_kernel;
+// the three share the projection, the window and the candidate test below: KeyFrame::IsInImage / GetFeaturesInArea
+// over the truncated bounds, the octave filter [level - 1, level], no chi-square test, no view of uright.  They are
+// siblings of fuse_point and not a parameter of it: as a template parameter they moved fuse_search_kernel's
+// registers (profiles/r15/disassembly.md).
+struct Sim3Probe {
+    float u, v, r;
+    int level;
+    uint4 d0, d1;
+};
+
+// keypoint k at CSR position j: the key, or kNone outside vIndices or the octave range; *in_area: it is in vIndices
+__device__ __forceinline__ uint32_t sim3_candidate_key(const Sim3Probe& p, const FrameView& V, int j, int k,
+                                                       bool* in_area) {
+    const spslam_keypoint kp = V.kun[k];
+    const float dx = __fsub_rn(kp.x, p.u), dy = __fsub_rn(kp.y, p.v);
+    if (!(fabsf(dx) < p.r && fabsf(dy) < p.r)) return kNone;
+    *in_area = true;
+    if (kp.octave < p.level - 1 || kp.octave > p.level) return kNone;
+    return ((uint32_t)hamming(p.d0, p.d1, V.desc + 32 * (size_t)k) << 20) | (uint32_t)j;
+}
+
+// The K smallest keys of the window over the cells x0 .. x1, y0 .. y1 (column-major, as GetFeaturesInArea scans
+// them, dealt to the point's kLGrp lanes and merged), in every lane of the point; taken (may be null): one byte per
+// keypoint, set ones are passed over.  Returns whether any keypoint, taken or not, is in vIndices.
+template <int K>
+__device__ __forceinline__ bool sim3_window_keys(const Sim3Probe& p, const FrameView& V, int x0, int x1, int y0, int y1,
+                                                 const uint8_t* taken, int sub, uint32_t (&bk)[K]) {
+#pragma unroll
+    for (int q = 0; q < K; q++) bk[q] = kNone;
+    bool any = false;
+    const int nrows = y1 - y0 + 1, ncells = x1 >= x0 && nrows > 0 ? (x1 - x0 + 1) * nrows : 0;
+    for (int cell = sub; cell < ncells; cell += kLGrp) {
+        const int cx = cell / nrows, c = (x0 + cx) * kRows + y0 + (cell - cx * nrows);
+        const int j0 = V.GO[c], j1 = V.GO[c + 1];
+        for (int j = j0; j < j1; j++) {
+            const int k = V.GI[j];
+            const uint32_t key = sim3_candidate_key(p, V, j, k, &any);
+            if (taken && taken[k]) continue;
+            insk(bk, key);
+        }
+    }
+    int anyi = any;
+#pragma unroll
+    for (int o = kLGrp / 2; o >= 1; o >>= 1) {
+        uint32_t pk[K];
+#pragma unroll
+        for (int q = 0; q < K; q++) pk[q] = (uint32_t)__shfl_xor((int)bk[q], o);
+#pragma unroll
+        for (int q = 0; q < K; q++) insk(bk, pk[q]);
+        anyi |= __shfl_xor(anyi, o);
+    }
+    return anyi != 0;
+}
+
+// cv::norm of a 3-vector: the squares summed in float, the root in double (local_window_kernel's reading)
+__device__ __forceinline__ float norm3f(const float* a) {
+    float sq = __fmul_rn(a[0], a[0]);
+    sq = __fadd_rn(sq, __fmul_rn(a[1], a[1]));
+    sq = __fadd_rn(sq, __fmul_rn(a[2], a[2]));
+    return (float)__dsqrt_rn((double)sq);
+}
+
+// The camera-frame point Pc into the keyframe: SPSLAM_FUSE_BEHIND, SPSLAM_FUSE_OUTSIDE_IMAGE or SPSLAM_FUSE_SEARCHED
+// with (u, v).  invz is 1/z in float (:331) or 1.0/z in double, rounded (:1019, :1166, :1246): the same bits, a
+// quotient rounded to 53 bits and then to 24 being the correctly rounded float.  u = fx*x+cx with GCC's contraction
+// (tests/test_loop_match_host.py).
+__device__ __forceinline__ int sim3_project(const float* Pc, const MatchGeom& g, float* u, float* v) {
+    if (Pc[2] < 0.0f) return SPSLAM_FUSE_BEHIND;
+    const float invz = __fdiv_rn(1.0f, Pc[2]);
+    const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
+    *u = __fmaf_rn(g.fx, x, g.cx);
+    *v = __fmaf_rn(g.fy, y, g.cy);
+    // KeyFrame::IsInImage: half open (KeyFrame.cc:627-630); z == 0 makes u / v inf or NaN, which fail it
+    if (!(*u >= g.min_x && *u < g.max_x && *v >= g.min_y && *v < g.max_y)) return SPSLAM_FUSE_OUTSIDE_IMAGE;
+    return SPSLAM_FUSE_SEARCHED;
+}
+
+__device__ __forceinline__ bool sim3_in_range(const spslam_local_point& p, float dist) {
+    const float maxD = __fmul_rn(1.2f, p.max_dist), minD = __fmul_rn(0.8f, p.min_dist);
+    return !(dist < minD || dist > maxD);
+}
+
+// PredictScale, the radius and GetFeaturesInArea's cell range; false: the reference's vIndices is empty
+__device__ __forceinline__ bool sim3_window(const spslam_local_point& p, float dist, float u, float v, const MatchGeom& g,
+                                            const FuseConsts& P, Sim3Probe* q, int* x0, int* x1, int* y0, int* y1) {
+    const int level = predict_scale(p.max_dist, dist, P.log_scale_factor, P.n_levels);
+    *q = Sim3Probe{u, v, __fmul_rn(P.th, level_entry(g.scale, level)), level, *(const uint4*)p.desc,
+                   *(const uint4*)(p.desc + 16)};
+    return cell_range(u, v, q->r, g, x0, x1, y0, y1);
+}
+
+// The decomposition of Scw (:298-303, :985-990) into the rows [Rcw | tcw] of T: scw = sqrt(sRcw.row(0).dot(sRcw.row(0)))
+// with Mat::dot summed in double and the root rounded to the float scw; Rcw = sRcw / scw and tcw = col3 / scw as
+// OpenCV's Mat / double, a scale by 1.0 / scw: the product with the double reciprocal, rounded once.
+__device__ __forceinline__ void sim3_decompose(const float* S, float* T) {
+    double d = __dmul_rn((double)S[0], (double)S[0]);
+    d = __dadd_rn(d, __dmul_rn((double)S[1], (double)S[1]));
+    d = __dadd_rn(d, __dmul_rn((double)S[2], (double)S[2]));
+    const float scw = (float)__dsqrt_rn(d);
+    const double inv = __ddiv_rn(1.0, (double)scw);
+#pragma unroll
+    for (int q = 0; q < 12; q++) T[q] = (float)__dmul_rn((double)S[q], inv);
+}
+
+// One point of SearchByProjection(pKF, Scw, ...) / Fuse(pKF, Scw, ...) up to its window (:312-362, :1000-1051, the
+// same statements): SPSLAM_FUSE_SEARCHED with the probe and the cell range, or the status of the test that ended it.
+// Ow = -Rcw.t()*tcw as fuse_point makes it.
+__device__ __forceinline__ int scw_window(const float* Scw, const spslam_local_point& p, const MatchGeom& g,
+                                          const FuseConsts& P, Sim3Probe* q, int* x0, int* x1, int* y0, int* y1) {
+    float T[12];
+    sim3_decompose(Scw, T);
+    const float tcw[3] = {T[3], T[7], T[11]};
+    float Pc[3], Ow[3], u, v;
+    mat3_mul(T, p.xw, tcw, false, 1.0, Pc);  // Rcw*p3Dw+tcw
+    q->level = 0;
+    const int st = sim3_project(Pc, g, &u, &v);
+    if (st != SPSLAM_FUSE_SEARCHED) return st;
+    mat3_mul(T, tcw, nullptr, true, -1.0, Ow);
+    const float PO[3] = {__fsub_rn(p.xw[0], Ow[0]), __fsub_rn(p.xw[1], Ow[1]), __fsub_rn(p.xw[2], Ow[2])};
+    const float dist = norm3f(PO);
+    if (!sim3_in_range(p, dist)) return SPSLAM_FUSE_OUT_OF_RANGE;
+    double dot = __dmul_rn((double)PO[0], (double)p.normal[0]);
+    dot = __dadd_rn(dot, __dmul_rn((double)PO[1], (double)p.normal[1]));
+    dot = __dadd_rn(dot, __dmul_rn((double)PO[2], (double)p.normal[2]));
+    if (dot < __dmul_rn(0.5, (double)dist)) return SPSLAM_FUSE_VIEW_ANGLE;  // doubles, no division
+    return sim3_window(p, dist, u, v, g, P, q, x0, x1, y0, y1) ? SPSLAM_FUSE_SEARCHED : SPSLAM_FUSE_NO_CANDIDATES;
+}
+
+// The search of Fuse(pKF, Scw, vpPoints, th, vpReplacePoint): fuse_search_kernel's records; the problem's Tcw field
+// holds Scw.  The walk :1082-1096 stays with the caller.
+__global__ __launch_bounds__(kThreads) void fuse_sim3_search_kernel(const spslam_fuse_problem* __restrict__ problems,
+                                                                    const spslam_local_point* __restrict__ points,
+                                                                    int max_points, MatchCurrent C, MatchGeom g,
+                                                                    FuseConsts P, const uint8_t* __restrict__ skip,
+                                                                    spslam_fuse_result* __restrict__ results,
+                                                                    int* __restrict__ nfused) {
+    const int f = blockIdx.x, sub = threadIdx.x & (kLGrp - 1);
+    const int i = blockIdx.y * kFusePtsPerBlock + (int)(threadIdx.x / kLGrp);
+    const spslam_fuse_problem& F = problems[f];
+    const bool live = i < F.n_points && i < max_points;  // uniform over the point's lanes
+    int status = SPSLAM_FUSE_SKIPPED, level = 0;
+    uint32_t bk[1] = {kNone};
+    const FrameView V = frame_view(C, F.kf_slot);
+    if (live && !(skip && skip[F.out_offset + i])) {
+        Sim3Probe q;
+        int x0, x1, y0, y1;
+        status = scw_window(F.Tcw, points[F.point_offset + i], g, P, &q, &x0, &x1, &y0, &y1);
+        level = q.level;
+        if (status == SPSLAM_FUSE_SEARCHED && !sim3_window_keys(q, V, x0, x1, y0, y1, nullptr, sub, bk))
+            status = SPSLAM_FUSE_NO_CANDIDATES;
+    }
+    const uint32_t best = bk[0];
+    const int dist = best != kNone ? (int)(best >> 20) : 256;
+    if (live && sub == 0) {
+        spslam_fuse_result r;
+        r.best_idx = best != kNone ? V.GI[best & 0xfffff] : -1;
+        r.best_dist = (int16_t)dist;
+        r.level = (uint8_t)level;
+        r.status = (uint8_t)status;
+        results[F.out_offset + i] = r;
+    }
+    const int n = wave_sum(live && sub == 0 && dist <= kThLow);  // nFused (:1082, :1095)
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&nfused[f], n);
+}
+
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th), the window kernel: per point the kSim3Keys smallest keys
+// among the keypoints that pass the octave filter and are not taken on entry, with the window for a re-scan.
+__global__ __launch_bounds__(kThreads) void proj_sim3_window_kernel(const spslam_fuse_problem* __restrict__ problems,
+                                                                    const spslam_local_point* __restrict__ points,
+                                                                    int max_points, MatchCurrent C, MatchGeom g,
+                                                                    FuseConsts P, const uint8_t* __restrict__ skip,
+                                                                    const uint8_t* __restrict__ taken_in,
+                                                                    Sim3Window* __restrict__ win) {
+    const int f = blockIdx.x, sub = threadIdx.x & (kLGrp - 1);
+    const int i = blockIdx.y * kFusePtsPerBlock + (int)(threadIdx.x / kLGrp);
+    const spslam_fuse_problem& F = problems[f];
+    if (i >= F.n_points || i >= max_points) return;  // uniform over the point's lanes
+    Sim3Window w{};
+#pragma unroll
+    for (int q = 0; q < kSim3Keys; q++) {
+        w.best[q] = kNone;
+        w.kp[q] = -1;
+    }
+    w.x0 = 1;  // an empty range
+    if (!(skip && skip[F.out_offset + i])) {
+        Sim3Probe q;
+        int x0, x1, y0, y1;
+        if (scw_window(F.Tcw, points[F.point_offset + i], g, P, &q, &x0, &x1, &y0, &y1) == SPSLAM_FUSE_SEARCHED) {
+            const FrameView V = frame_view(C, F.kf_slot);
+            uint32_t bk[kSim3Keys];
+            sim3_window_keys(q, V, x0, x1, y0, y1, taken_in ? taken_in + (size_t)f * C.cap : nullptr, sub, bk);
+            w.u = q.u; w.v = q.v; w.r = q.r;
+            w.level = (int8_t)q.level;
+            w.valid = 1;
+            w.x0 = (int16_t)x0; w.x1 = (int16_t)x1; w.y0 = (int16_t)y0; w.y1 = (int16_t)y1;
+#pragma unroll
+            for (int k = 0; k < kSim3Keys; k++) {
+                w.best[k] = bk[k];
+                if (bk[k] != kNone) w.kp[k] = V.GI[bk[k] & 0xfffff];
+            }
+        }
+    }
+    if (sub == 0) win[(size_t)f * max_points + i] = w;
+}
+
+// ... and its in-order walk, one wave per problem (:312-400): point i takes the best of its keypoints still free, if
+// that distance is <= TH_LOW.  The lanes hold 64 consecutive points; in passes, every point not yet decided picks the
+// first of its keys that is free, the accepting ones claim their keypoint (LDS atomicMin of the lane), and the points
+// before the first one that lost a claim, or whose keys are all taken, are committed together.  A loser starts the
+// next pass (its key is taken by then); a point out of keys is re-scanned by the whole wave, and only when its last
+// key could still be accepted: the keys ascend, so past a distance above TH_LOW nothing can.
+__global__ __launch_bounds__(64) void proj_sim3_assign_kernel(const spslam_fuse_problem* __restrict__ problems,
+                                                              const spslam_local_point* __restrict__ points,
+                                                              int max_points, MatchCurrent C,
+                                                              const uint8_t* __restrict__ taken_in,
+                                                              const Sim3Window* __restrict__ win,
+                                                              int32_t* __restrict__ match, int* __restrict__ nmatches) {
+    extern __shared__ uint32_t taken[];  // [ceil(cap / 32)], then claim[cap]
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const spslam_fuse_problem& F = problems[f];
+    const int n_kp = min(C.counts[F.kf_slot], C.cap), np = min(F.n_points, max_points);
+    int32_t* M = match + (size_t)f * C.cap;
+    const int words = (C.cap + 31) / 32;
+    uint32_t* claim = taken + words;
+    const uint8_t* tk = taken_in ? taken_in + (size_t)f * C.cap : nullptr;
+    for (int k = lane; k < n_kp; k += 64) {
+        claim[k] = ~0u;
+        M[k] = -1;
+    }
+    for (int wd = lane; wd < words; wd += 64) {
+        uint32_t bits = 0u;
+        if (tk)
+            for (int b = 0; b < 32; b++) {
+                const int k = 32 * wd + b;
+                if (k < n_kp && tk[k]) bits |= 1u << b;
+            }
+        taken[wd] = bits;
+    }
+    __syncthreads();
+    const Sim3Window* Wf = win + (size_t)f * max_points;
+    const FrameView V = frame_view(C, F.kf_slot);
+    const spslam_local_point* Pp = points + F.point_offset;
+    int nm = 0;
+    for (int c0 = 0; c0 < np; c0 += 64) {
+        const int i = c0 + lane, m = min(64, np - c0);
+        uint32_t best[kSim3Keys];
+        int b[kSim3Keys];
+#pragma unroll
+        for (int q = 0; q < kSim3Keys; q++) {
+            best[q] = kNone;
+            b[q] = -1;
+        }
+        if (i < np) {
+            const Sim3Window w = Wf[i];
+#pragma unroll
+            for (int q = 0; q < kSim3Keys; q++) {
+                best[q] = w.valid ? w.best[q] : kNone;
+                b[q] = best[q] != kNone ? w.kp[q] : -1;
+            }
+        }
+        int start = 0;
+        while (start < m) {
+            const bool act = lane >= start && lane < m;
+            uint32_t k1 = kNone;
+            int b1 = -1;
+            if (act) {
+#pragma unroll
+                for (int q = kSim3Keys - 1; q >= 0; q--)
+                    if (best[q] != kNone && !bit_test(taken, b[q])) { k1 = best[q]; b1 = b[q]; }
+            }
+            // out of keys: all kSim3Keys were there, all are taken, and the last could still have been accepted
+            const bool out = act && k1 == kNone && best[kSim3Keys - 1] != kNone &&
+                             (int)(best[kSim3Keys - 1] >> 20) <= kThLow;
+            const bool acc = act && k1 != kNone && (int)(k1 >> 20) <= kThLow;  // :394
+            if (acc) atomicMin(&claim[b1], (uint32_t)lane);
+            wave_sync();
+            const bool lost = acc && claim[b1] < (uint32_t)lane;
+            wave_sync();
+            if (acc) claim[b1] = ~0u;
+            const unsigned long long sm = __ballot(out || lost);
+            const int first = sm ? __ffsll((long long)sm) - 1 : m;
+            const bool commit = acc && lane < first;
+            if (commit) {
+                M[b1] = c0 + lane;  // vpMatched[bestIdx] = pMP (:396)
+                bit_set_atomic(taken, b1);
+            }
+            nm += __popcll(__ballot(commit));
+            wave_sync();
+            if (first >= m) break;
+            start = first;
+            if (!__shfl((int)out, first)) continue;  // lost a claim: decided by the next pass
+            start = first + 1;
+            const Sim3Window w = Wf[c0 + first];
+            const uint8_t* d = Pp[c0 + first].desc;
+            const Sim3Probe q{w.u, w.v, w.r, w.level, *(const uint4*)d, *(const uint4*)(d + 16)};
+            uint32_t k = kNone;
+            bool any = false;
+            for (int ix = w.x0; ix <= w.x1; ix++)
+                for (int iy = w.y0; iy <= w.y1; iy++) {
+                    const int c = ix * kRows + iy;
+                    for (int j = V.GO[c] + lane; j < V.GO[c + 1]; j += 64) {
+                        const int kk = V.GI[j];
+                        if (bit_test(taken, kk)) continue;
+                        k = min(k, sim3_candidate_key(q, V, j, kk, &any));
+                    }
+                }
+            k = wave_min(k);
+            if (k == kNone || (int)(k >> 20) > kThLow) continue;
+            if (lane == 0) {
+                const int kk = V.GI[k & 0xfffff];
+                M[kk] = c0 + first;
+                bit_set(taken, kk);
+            }
+            nm++;
+            wave_sync();
+        }
+    }
+    if (lane == 0) nmatches[f] = nm;
+}
+
+// SearchBySim3, the two searches (:1148-1305) in one launch: blockIdx.z = 0 sends KF1's map points into KF2 by
+// sR21 / t21 (vnMatch1), 1 sends KF2's into KF1 by sR12 / t12 (vnMatch2).  sR12 = s12*R12 (a float product in
+// double, rounded: the float product), sR21 = (1.0/s12)*R12.t() (the double reciprocal times the element, rounded
+// once) and t21 = -sR21*t12 (rows summed in double, negated, rounded) are made here.  The distance
+// is cv::norm of the camera-frame point; no view-angle test.  A point is passed over without a map point, with a
+// bad one, or (side 1) already matched on entry; side 2's vbAlreadyMatched2 is applied by the agreement pass,
+// which is all that reads vnMatch2.  vn at pair * 2 * cap: vnMatch1, then vnMatch2.
+__global__ __launch_bounds__(kThreads) void sim3_search_kernel(const spslam_sim3_pair* __restrict__ pairs,
+                                                               spslam_sim3_map map, MatchCurrent C, MatchGeom g,
+                                                               FuseConsts P, const int32_t* __restrict__ match12,
+                                                               int32_t* __restrict__ vn) {
+    const int p = blockIdx.x, side = blockIdx.z, sub = threadIdx.x & (kLGrp - 1);
+    const int i = blockIdx.y * kFusePtsPerBlock + (int)(threadIdx.x / kLGrp);
+    const spslam_sim3_pair& S = pairs[p];
+    const int kf_from = side ? S.kf2 : S.kf1, kf_to = side ? S.kf1 : S.kf2;
+    const int slot_from = map.kf_slot[kf_from], slot_to = map.kf_slot[kf_to];
+    const int n_from = min(min(C.counts[slot_from], C.cap), map.match_off[kf_from + 1] - map.match_off[kf_from]);
+    if (i >= n_from) return;  // uniform over the point's lanes
+    uint32_t bk[1] = {kNone};
+    const FrameView V = frame_view(C, slot_to);
+    const int row = map.match_row[map.match_off[kf_from] + i];
+    do {
+        if (row < 0 || (map.point_bad && map.point_bad[row])) break;       // :1152-1156
+        if (side == 0 && match12[S.match_offset + i] >= 0) break;         // vbAlreadyMatched1
+        const spslam_local_point& pt = map.points[row];
+        // the transform between the cameras, rows [sR | t] at stride 4
+        float A[12];
+        if (side == 0) {
+            const double inv = __ddiv_rn(1.0, (double)S.s12);
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) A[4 * r + c] = (float)__dmul_rn((double)S.R12[3 * c + r], inv);
+            float t21[3];
+            mat3_mul(A, S.t12, nullptr, false, -1.0, t21);
+            A[3] = t21[0]; A[7] = t21[1]; A[11] = t21[2];
+        } else {
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) A[4 * r + c] = __fmul_rn(S.s12, S.R12[3 * r + c]);
+                A[4 * r + 3] = S.t12[r];
+            }
+        }
+        const float* Tw = map.kf_Tcw + 16 * (size_t)kf_from;
+        const float tw[3] = {Tw[3], Tw[7], Tw[11]}, ta[3] = {A[3], A[7], A[11]};
+        float Pa[3], Pb[3], u, v;
+        mat3_mul(Tw, pt.xw, tw, false, 1.0, Pa);   // R1w*p3Dw + t1w
+        mat3_mul(A, Pa, ta, false, 1.0, Pb);       // sR21*p3Dc1 + t21
+        if (sim3_project(Pb, g, &u, &v) != SPSLAM_FUSE_SEARCHED) break;
+        const float dist = norm3f(Pb);
+        if (!sim3_in_range(pt, dist)) break;
+        Sim3Probe q;
+        int x0, x1, y0, y1;
+        if (!sim3_window(pt, dist, u, v, g, P, &q, &x0, &x1, &y0, &y1)) break;
+        sim3_window_keys(q, V, x0, x1, y0, y1, nullptr, sub, bk);
+    } while (false);
+    if (sub == 0) {
+        const uint32_t best = bk[0];
+        const bool ok = best != kNone && (int)(best >> 20) <= kThHigh;     // :1221
+        vn[((size_t)p * 2 + side) * C.cap + i] = ok ? V.GI[best & 0xfffff] : -1;
+    }
+}
+
+// ... and the agreement pass (:1307-1323), one workgroup per pair: vbAlreadyMatched2 from match12 as it came in (or
+// the caller's override), then match12[i1] = idx2 where vnMatch1[i1] = idx2 and vnMatch2[idx2] = i1 with idx2 not
+// already matched.  flags: cap bytes per pair.
+__global__ __launch_bounds__(kThreads) void sim3_agree_kernel(const spslam_sim3_pair* __restrict__ pairs,
+                                                              spslam_sim3_map map, MatchCurrent C,
+                                                              const uint8_t* __restrict__ already2,
+                                                              const int32_t* __restrict__ vn,
+                                                              uint8_t* __restrict__ flags, int32_t* __restrict__ match12,
+                                                              int* __restrict__ n_found) {
+    __shared__ int found;
+    const int p = blockIdx.x, t = threadIdx.x;
+    const spslam_sim3_pair& S = pairs[p];
+    const int n1 = min(min(C.counts[map.kf_slot[S.kf1]], C.cap), map.match_off[S.kf1 + 1] - map.match_off[S.kf1]);
+    const int n2 = min(min(C.counts[map.kf_slot[S.kf2]], C.cap), map.match_off[S.kf2 + 1] - map.match_off[S.kf2]);
+    const int32_t* vn1 = vn + (size_t)p * 2 * C.cap;
+    const int32_t* vn2 = vn1 + C.cap;
+    uint8_t* fl = flags + (size_t)p * C.cap;
+    int32_t* M = match12 + S.match_offset;
+    if (t == 0) found = 0;
+    for (int k = t; k < n2; k += kThreads) fl[k] = already2 ? already2[(size_t)p * C.cap + k] : 0;
+    __syncthreads();
+    if (!already2)
+        for (int i = t; i < n1; i += kThreads) {
+            const int idx2 = M[i];
+            if (idx2 >= 0 && idx2 < n2) fl[idx2] = 1;                      // :1138-1140
+        }
+    __syncthreads();
+    int n = 0;
+    for (int i = t; i < n1; i += kThreads) {
+        const int idx2 = vn1[i];
+        if (idx2 >= 0 && idx2 < n2 && !fl[idx2] && vn2[idx2] == i) {
+            M[i] = idx2;
+            n++;
+        }
+    }
+    if (n) atomicAdd(&found, n);
+    __syncthreads();
+    if (t == 0) n_found[S.result_offset] = found;
+}
+
 }  // namespace match
 
 // Dynamic LDS beyond the default 64 KB needs the per-kernel opt-in: both instantiations (K keys per point) of a walk.
@@ -899,6 +1329,52 @@ hipError_t fuse_search_launch(int n_problems, const spslam_fuse_problem* problem
         hipLaunchKernelGGL(match::fuse_search_kernel,
                            dim3(n_problems, (max_points + match::kFusePtsPerBlock - 1) / match::kFusePtsPerBlock),
                            dim3(match::kThreads), 0, s, problems, points, max_points, cur, g, P, skip, results, nfused);
+    return hipGetLastError();
+}
+
+hipError_t fuse_sim3_search_launch(int n_problems, const spslam_fuse_problem* problems,
+                                   const spslam_local_point* points, int max_points, const MatchCurrent& cur,
+                                   const MatchGeom& g, const FuseConsts& P, const uint8_t* skip,
+                                   spslam_fuse_result* results, int* nfused, hipStream_t s) {
+    if (n_problems < 1 || max_points < 0 || cur.cap < 1) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(nfused, 0, (size_t)n_problems * sizeof(int), s);
+    if (e != hipSuccess) return e;
+    if (max_points > 0)
+        hipLaunchKernelGGL(match::fuse_sim3_search_kernel,
+                           dim3(n_problems, (max_points + match::kFusePtsPerBlock - 1) / match::kFusePtsPerBlock),
+                           dim3(match::kThreads), 0, s, problems, points, max_points, cur, g, P, skip, results, nfused);
+    return hipGetLastError();
+}
+
+hipError_t proj_sim3_launch(int n_problems, const spslam_fuse_problem* problems, const spslam_local_point* points,
+                            int max_points, const MatchCurrent& cur, const MatchGeom& g, const FuseConsts& P,
+                            const uint8_t* skip, const uint8_t* taken_in, Sim3Window* win, int32_t* match,
+                            int* nmatches, hipStream_t s) {
+    // taken bits + the claim table in dynamic LDS (opted in up to 150 KB: caps up to ~36K keypoints)
+    const size_t lds = (size_t)((cur.cap + 31) / 32) * 4 + (size_t)cur.cap * 4;
+    if (n_problems < 1 || max_points < 0 || cur.cap < 1 || lds > 150 * 1024) return hipErrorInvalidValue;
+    static const hipError_t lds_attr = hipFuncSetAttribute((const void*)match::proj_sim3_assign_kernel,
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (lds_attr != hipSuccess) return lds_attr;
+    if (max_points > 0)
+        hipLaunchKernelGGL(match::proj_sim3_window_kernel,
+                           dim3(n_problems, (max_points + match::kFusePtsPerBlock - 1) / match::kFusePtsPerBlock),
+                           dim3(match::kThreads), 0, s, problems, points, max_points, cur, g, P, skip, taken_in, win);
+    hipLaunchKernelGGL(match::proj_sim3_assign_kernel, dim3(n_problems), dim3(64), lds, s, problems, points,
+                       max_points, cur, taken_in, win, match, nmatches);
+    return hipGetLastError();
+}
+
+hipError_t sim3_search_launch(int n_pairs, const spslam_sim3_pair* pairs, const spslam_sim3_map& map,
+                              const MatchCurrent& cur, const MatchGeom& g, const FuseConsts& P,
+                              const uint8_t* already2, int32_t* vn, uint8_t* flags, int32_t* match12, int* n_found,
+                              hipStream_t s) {
+    if (n_pairs < 1 || cur.cap < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(match::sim3_search_kernel,
+                       dim3(n_pairs, (cur.cap + match::kFusePtsPerBlock - 1) / match::kFusePtsPerBlock, 2),
+                       dim3(match::kThreads), 0, s, pairs, map, cur, g, P, match12, vn);
+    hipLaunchKernelGGL(match::sim3_agree_kernel, dim3(n_pairs), dim3(match::kThreads), 0, s, pairs, map, cur,
+                       already2, vn, flags, match12, n_found);
     return hipGetLastError();
 }
 

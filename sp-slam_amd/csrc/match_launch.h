@@ -76,6 +76,39 @@ hipError_t fuse_search_launch(int n_problems, const spslam_fuse_problem* problem
                               int max_points, const MatchCurrent& cur, const MatchGeom& g, const FuseConsts& P,
                               const uint8_t* skip, spslam_fuse_result* results, int* nfused, hipStream_t s);
 
+// LoopClosing's Sim3 matchers.  g: the KeyFrame's geometry, as for fuse_search_launch; P.inv_sigma2 is not read.
+// Fuse(pKF, Scw, ...)'s search: fuse_search_launch's records, the problems' Tcw fields holding Scw; cur.uright is
+// not read (may be null).
+hipError_t fuse_sim3_search_launch(int n_problems, const spslam_fuse_problem* problems,
+                                   const spslam_local_point* points, int max_points, const MatchCurrent& cur,
+                                   const MatchGeom& g, const FuseConsts& P, const uint8_t* skip,
+                                   spslam_fuse_result* results, int* nfused, hipStream_t s);
+
+// Per-point search state of SearchByProjection(pKF, Scw, ...) between its two kernels (scratch, n_problems *
+// max_points entries): the window and the kSim3Keys smallest keys among the keypoints not taken on entry.  The
+// in-order walk re-scans a window only when in-loop assignments took all of them.
+constexpr int kSim3Keys = SPSLAM_PROJ_SIM3_KEYS;
+struct Sim3Window {
+    float u, v, r;
+    int16_t x0, x1, y0, y1;  // GetFeaturesInArea cell range (x0 > x1: empty)
+    int8_t level, valid, pad[2];
+    uint32_t best[kSim3Keys];  // (distance << 20) | CSR position, ascending; ~0u: none
+    int32_t kp[kSim3Keys];     // their keypoints, -1: none
+};
+
+// taken_in (may be null) and match at problem * cur.cap; nmatches one int per problem.
+hipError_t proj_sim3_launch(int n_problems, const spslam_fuse_problem* problems, const spslam_local_point* points,
+                            int max_points, const MatchCurrent& cur, const MatchGeom& g, const FuseConsts& P,
+                            const uint8_t* skip, const uint8_t* taken_in, Sim3Window* win, int32_t* match,
+                            int* nmatches, hipStream_t s);
+
+// SearchBySim3: vn (2 * cur.cap ints per pair) and flags (cur.cap bytes per pair) are scratch; already2 (may be
+// null) at pair * cur.cap.
+hipError_t sim3_search_launch(int n_pairs, const spslam_sim3_pair* pairs, const spslam_sim3_map& map,
+                              const MatchCurrent& cur, const MatchGeom& g, const FuseConsts& P,
+                              const uint8_t* already2, int32_t* vn, uint8_t* flags, int32_t* match12, int* n_found,
+                              hipStream_t s);
+
 hipError_t match_launch(int n_frames, const spslam_proj_frame* frames, const spslam_proj_point* points,
                         int max_points, const MatchCurrent& cur, const MatchGeom& g, const spslam_match_params& P,
                         MatchWindow* win, int2* pushes, int32_t* match, int* nmatches, hipStream_t s,
