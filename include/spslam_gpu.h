@@ -1779,8 +1779,9 @@ int spslam_place_min_score(spslam_ctx* ctx, const spslam_place_db* db, int n_kf,
  *   SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)    src/ORBmatcher.cc:1102-1326 (LoopClosing.cc:325)
  *   SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)       src/ORBmatcher.cc:290-403   (LoopClosing.cc:393)
  *   Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)                src/ORBmatcher.cc:977-1100  (LoopClosing.cc:700)
- * All four are deterministic.  Sim3Solver, OptimizeSim3, the consistency groups and CorrectLoop's map mutation stay
- * with the caller.  None of these entries has a timing kind, and none is part of the batched step.
+ * All four are deterministic, and so is Sim3Solver (src/Sim3Solver.cc, LoopClosing.cc:276-324) once its rand() draws
+ * are an input: it sits between the first two.  OptimizeSim3, the consistency groups and CorrectLoop's map mutation
+ * stay with the caller.  None of these entries has a timing kind, and none is part of the batched step.
  * KeyFrame's image bounds are ints (include/KeyFrame.h:198-201): the configured bounds are truncated, as for
  * spslam_fuse_search.  The host-pointer forms take one problem and check every index before anything is launched
  * (SPSLAM_ERR_ARG on a violation). */
@@ -1875,6 +1876,86 @@ int spslam_search_by_sim3(spslam_ctx* ctx, const spslam_sim3_keyframe* kf1, cons
                           const spslam_local_point* points, const uint8_t* point_bad, int n_rows,
                           const spslam_sim3_pair* pair, const uint8_t* already2, const spslam_sim3_params* params,
                           int32_t* match12, int* n_found);
+
+/* ---- Sim3Solver (src/Sim3Solver.cc), as ComputeSim3 uses it between SearchByBoW and SearchBySim3: the
+ * constructor, SetRansacParameters, iterate and GetEstimated*.  Semantics: tests/sim3_solver_ref.py.
+ * The solver draws from rand(): the draws are an input here.  The caller records 3 * max_iterations raw rand()
+ * values per problem; iteration k, counted from 0 over the solver's life, uses values 3k .. 3k+2 for its three
+ * RandomInt(0, size - 1) = int((double)r / ((double)rand_max + 1.0) * size).  All hypotheses of a call are
+ * evaluated, then the first one at which the reference's sequential loop returns is selected. */
+#define SPSLAM_SIM3_FOUND 0      /* iterate returned a transformation */
+#define SPSLAM_SIM3_NOT_YET 1    /* empty Mat, bNoMore false */
+#define SPSLAM_SIM3_NO_MORE 2    /* empty Mat, bNoMore true: N < min_inliers, or mRansacMaxIts reached */
+#define SPSLAM_SIM3_MAX_ITERATIONS 4096
+
+typedef struct spslam_sim3_problem {
+    int32_t kf1, kf2;          /* keyframe indices of the map */
+    int32_t match_offset;      /* vpMatched12: the keyframe's N1 ints at d_match12 (and d_match12_out) + match_offset */
+    int32_t rand_offset;       /* 3 * max_iterations ints at d_rand + rand_offset */
+    int32_t inlier_offset;     /* vbInliers: N1 bytes at d_inliers + inlier_offset */
+    int32_t iterations_done;   /* mnIterations on entry (0 for a new solver) */
+    int32_t best_inliers;      /* mnBestInliers on entry (0 for a new solver) */
+    int32_t n_iterations;      /* iterate's nIterations */
+} spslam_sim3_problem;         /* 32 bytes */
+
+typedef struct spslam_sim3_result {
+    int32_t status;            /* SPSLAM_SIM3_* */
+    int32_t n;                 /* N: the correspondences the constructor kept */
+    int32_t iterations_done;   /* mnIterations on exit */
+    int32_t best_inliers;      /* mnBestInliers on exit */
+    int32_t n_inliers;         /* nInliers (0 unless FOUND) */
+    float s12;                 /* GetEstimatedScale; this and what follows are 0 unless FOUND */
+    float R12[9];              /* GetEstimatedRotation, row-major */
+    float t12[3];              /* GetEstimatedTranslation */
+    float T12[16];             /* the returned Mat, row-major */
+} spslam_sim3_result;          /* 136 bytes */
+
+typedef struct spslam_sim3_solver_params {
+    int32_t min_inliers;       /* mRansacMinInliers (20 in ComputeSim3), >= 3 */
+    int32_t max_iterations;    /* SetRansacParameters' maxIterations (300), 1 .. SPSLAM_SIM3_MAX_ITERATIONS */
+    int32_t rand_max;          /* the caller's RAND_MAX */
+    int32_t fix_scale;         /* mbFixScale (RGB-D: 1) */
+} spslam_sim3_solver_params;
+
+/* SetRansacParameters (:114-138) for every N a keyframe can give: table[n] = mRansacMaxIts for N = n, n in
+ * [min_inliers, cap], with the reference's expression on the host's libm (epsilon in float, pow and log in double,
+ * ceil, 1 when N == min_inliers, max(1, min(., max_iterations))); 0 below min_inliers, where iterate returns at
+ * once.  table: cap + 1 ints.  A quotient that no int holds counts as max_iterations. */
+int spslam_sim3_ransac_table(double probability, int min_inliers, int max_iterations, int cap, int32_t* table);
+
+/* Batched, device resident.  Problem p reads its keyframes from the map and the slots, d_match12 as
+ * spslam_search_by_bow_kf_batch_device left it, and its draws.  The constructor keeps keypoint i1 of KF1, in
+ * order, when match12[i1] is a keypoint of KF2, both keypoints have a map point (match_row >= 0) and neither point
+ * is bad.  CONTRACT, as for SearchBySim3: the points' GetIndexInKeyFrame are i1 and match12[i1].  d_max_its_table:
+ * cap + 1 ints of spslam_sim3_ransac_table for the same min_inliers and max_iterations.  The camera and
+ * mvLevelSigma2 are the context's; octaves outside the configured levels read level 0.
+ * Outputs: d_results[p]; d_inliers (always written: N1 bytes, zero unless FOUND).  d_pairs_out and d_match12_out
+ * may be NULL; given, a FOUND problem p gets d_pairs_out[p] = {kf1, kf2, match_offset, result_offset = p, s12, R12,
+ * t12} and, at d_match12_out + match_offset, match12 with every entry that is no inlier set to -1
+ * (LoopClosing.cc:315-320): what spslam_search_by_sim3_batch_device takes on the same stream.  Problems that are
+ * not FOUND leave both as they were.  A draw outside [0, rand_max] is clamped into the list it indexes.
+ * cap <= 8192.  The call keeps 16 + 56 * cap + 64 * max_iterations bytes of scratch per problem in the context,
+ * the buffer the other loop-closing searches use: calls that share a context are ordered on one stream. */
+int spslam_sim3_solver_batch_device(spslam_ctx* ctx, int n_problems, const spslam_sim3_problem* d_problems,
+                                    const spslam_sim3_map* map, const spslam_keypoint* d_keys_un, const int* d_counts,
+                                    int cap, const int32_t* d_match12, const int32_t* d_rand,
+                                    const int32_t* d_max_its_table, const spslam_sim3_solver_params* params,
+                                    spslam_sim3_result* d_results, uint8_t* d_inliers, spslam_sim3_pair* d_pairs_out,
+                                    int32_t* d_match12_out, void* hip_stream);
+
+/* Drop-in for one problem on host buffers: the keyframes' Tcw, keys_un, match_row and n are read (the grid and the
+ * descriptors are not); match12: kf1->n ints in [-1, kf2->n); rand: 3 * max_iterations values in [0, rand_max];
+ * *iterations_done and *best_inliers are the solver's state, read and rewritten; inliers: kf1->n bytes;
+ * match12_out (may be NULL): kf1->n ints, written when the status is FOUND.  Every index is checked before anything
+ * is launched: match12, match_row, the octaves against the configured levels, min_inliers >= 3, n_iterations >= 0. */
+int spslam_sim3_solver(spslam_ctx* ctx, const spslam_sim3_keyframe* kf1, const spslam_sim3_keyframe* kf2,
+                       const spslam_local_point* points, const uint8_t* point_bad, int n_rows,
+                       const int32_t* match12, const int32_t* rand, const spslam_sim3_solver_params* params,
+                       double probability, int n_iterations, int* iterations_done, int* best_inliers,
+                       spslam_sim3_result* result, uint8_t* inliers, int32_t* match12_out);
+
+/* Test hook: fills the loop-closing scratch of the context with a byte value (results must not depend on it). */
+int spslam_debug_fill_loop_scratch(spslam_ctx* ctx, int value);
 
 /* ---- SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) and the search of Fuse(pKF, Scw, vpPoints, th,
  * vpReplacePoint).  Both take spslam_fuse_problem records whose Tcw field holds Scw; the decomposition (:298-303,

@@ -1,10 +1,12 @@
 // C ABI (include/spslam_gpu.h), LoopClosing's ORBmatcher side (ComputeSim3, SearchAndFuse):
 // spslam_search_by_bow_kf[_batch_device] (SearchByBoW(KeyFrame*, KeyFrame*)), spslam_search_by_sim3[_batch_device]
 // (SearchBySim3), spslam_search_by_projection_sim3[_batch_device] (SearchByProjection(pKF, Scw, ...)) and
-// spslam_fuse_sim3_search[_batch_device] (the search of Fuse(pKF, Scw, ...)).  The host forms check their indices
-// with loop_check.h before anything is staged.
+// spslam_fuse_sim3_search[_batch_device] (the search of Fuse(pKF, Scw, ...)), and Sim3Solver between the first two:
+// spslam_sim3_ransac_table, spslam_sim3_solver[_batch_device].  The host forms check their indices with loop_check.h
+// before anything is staged.
 #include "capi_ctx.h"
 #include "loop_check.h"
+#include "sim3_launch.h"
 
 #include <cmath>
 #include <cstring>
@@ -201,6 +203,127 @@ int spslam_search_by_sim3(spslam_ctx* c, const spslam_sim3_keyframe* kf1, const 
     HIP_CHECK(c, hipMemcpyAsync(n_found, st.slot<int>(kFound), 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = st.close())) return rc;
     HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return SPSLAM_OK;
+}
+
+// ---------------------------------------------------------------- Sim3Solver
+int spslam_sim3_ransac_table(double probability, int min_inliers, int max_iterations, int cap, int32_t* table) {
+    if (!table || cap < 0 || min_inliers < 1 || max_iterations < 1) return SPSLAM_ERR_ARG;
+    for (int n = 0; n <= cap; n++) {
+        if (n < min_inliers) { table[n] = 0; continue; }
+        double its = 1.0;                                                      // :130-131
+        if (n != min_inliers) {
+            const float epsilon = (float)min_inliers / n;                      // :125
+            its = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3)));   // :133
+        }
+        const int n_iterations = its < (double)max_iterations ? (int)its : max_iterations;   // min(nIterations, mRansacMaxIts)
+        table[n] = std::max(1, n_iterations);
+    }
+    return SPSLAM_OK;
+}
+
+int spslam_sim3_solver_batch_device(spslam_ctx* c, int n_problems, const spslam_sim3_problem* d_problems,
+                                    const spslam_sim3_map* map, const spslam_keypoint* d_keys_un, const int* d_counts,
+                                    int cap, const int32_t* d_match12, const int32_t* d_rand,
+                                    const int32_t* d_max_its_table, const spslam_sim3_solver_params* params,
+                                    spslam_sim3_result* d_results, uint8_t* d_inliers, spslam_sim3_pair* d_pairs_out,
+                                    int32_t* d_match12_out, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    if (n_problems < 1 || n_problems > 65535 || !d_problems || !map || !map->kf_Tcw || !map->kf_slot ||
+        !map->match_off || !map->match_row || !map->points || !d_keys_un || !d_counts || cap < 1 || cap > 8192 ||
+        !d_match12 || !d_rand || !d_max_its_table || !params || params->min_inliers < 3 ||
+        params->max_iterations < 1 || params->max_iterations > SPSLAM_SIM3_MAX_ITERATIONS || params->rand_max < 1 ||
+        !d_results || !d_inliers)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_sim3_solver_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    SolverConsts P{};
+    P.fx = c->fg.fx; P.fy = c->fg.fy; P.cx = c->fg.cx; P.cy = c->fg.cy;
+    for (int l = 0; l < 8; l++)  // mvnMaxError is a vector<size_t>: the double product truncated (:87-88)
+        P.max_error[l] = l < c->p.nlevels ? (float)(size_t)(9.210 * c->sigma2[l]) : 0.f;
+    P.min_inliers = params->min_inliers; P.max_iterations = params->max_iterations;
+    P.rand_max = params->rand_max; P.fix_scale = params->fix_scale;
+    HIP_CHECK(c, c->d_loop_scratch.reserve(sim3_scratch_bytes(n_problems, cap, params->max_iterations), s));
+    HIP_CHECK(c, sim3_solver_launch(n_problems, d_problems, *map, d_keys_un, d_counts, cap, d_match12, d_rand,
+                                    d_max_its_table, P, c->d_loop_scratch.p, d_results, d_inliers, d_pairs_out,
+                                    d_match12_out, s));
+    return SPSLAM_OK;
+}
+
+int spslam_sim3_solver(spslam_ctx* c, const spslam_sim3_keyframe* kf1, const spslam_sim3_keyframe* kf2,
+                       const spslam_local_point* points, const uint8_t* point_bad, int n_rows,
+                       const int32_t* match12, const int32_t* rand, const spslam_sim3_solver_params* params,
+                       double probability, int n_iterations, int* iterations_done, int* best_inliers,
+                       spslam_sim3_result* result, uint8_t* inliers, int32_t* match12_out) {
+    if (!c || !result || n_rows < 0 || (n_rows && !points)) return SPSLAM_ERR_ARG;
+    const spslam_sim3_keyframe* k[2] = {kf1, kf2};
+    for (int s = 0; s < 2; s++)
+        if (const char* e = loop_check_solver_keyframe(k[s], n_rows, c->p.nlevels)) return fail(c, SPSLAM_ERR_ARG, "spslam_sim3_solver: %s", e);
+    if (const char* e = loop_check_match12(match12, kf1->n, kf2->n)) return fail(c, SPSLAM_ERR_ARG, "spslam_sim3_solver: %s", e);
+    if (const char* e = loop_check_solver_call(params, probability, n_iterations, iterations_done, best_inliers, rand))
+        return fail(c, SPSLAM_ERR_ARG, "spslam_sim3_solver: %s", e);
+    if (kf1->n && !inliers) return fail(c, SPSLAM_ERR_ARG, "spslam_sim3_solver: %s", "inliers is missing");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    // the two keyframes as slots 0 and 1 of cap keypoints, keyframes 0 and 1 of a two-keyframe map
+    const int cap = std::max(std::max(kf1->n, kf2->n), 1);
+    const size_t C = (size_t)cap, R = (size_t)std::max(n_rows, 1);
+    std::vector<spslam_keypoint> kun(2 * C);
+    std::vector<int32_t> rows(2 * C, -1), table(C + 1);
+    float Tcw[32];
+    const int32_t counts[2] = {kf1->n, kf2->n}, slot[2] = {0, 1}, off[3] = {0, cap, 2 * cap};
+    for (int s = 0; s < 2; s++) {
+        if (k[s]->n) {
+            std::memcpy(kun.data() + s * C, k[s]->keys_un, (size_t)k[s]->n * sizeof(spslam_keypoint));
+            std::memcpy(rows.data() + s * C, k[s]->match_row, (size_t)k[s]->n * 4);
+        }
+        std::memcpy(Tcw + 16 * s, k[s]->Tcw, 64);
+    }
+    spslam_sim3_ransac_table(probability, params->min_inliers, params->max_iterations, cap, table.data());
+    spslam_sim3_problem Q{};
+    Q.kf1 = 0; Q.kf2 = 1;
+    Q.iterations_done = *iterations_done; Q.best_inliers = *best_inliers; Q.n_iterations = n_iterations;
+    enum { kKun, kCounts, kTcw, kSlot, kOff, kRows, kBad, kPoints, kProblem, kMatch, kRand, kTable, kResult, kInliers,
+           kMatchOut };
+    Stage st(c);
+    if (int rc = st.open({{kun.data(), kun.size() * sizeof(spslam_keypoint)}, {counts, 8}, {Tcw, 128}, {slot, 8},
+                          {off, 12}, {rows.data(), rows.size() * 4}, {point_bad, point_bad ? (size_t)n_rows : 0, R},
+                          {points, (size_t)n_rows * sizeof(spslam_local_point), R * sizeof(spslam_local_point)},
+                          {&Q, sizeof Q}, {match12, (size_t)kf1->n * 4, C * 4},
+                          {rand, (size_t)params->max_iterations * 12}, {table.data(), table.size() * 4},
+                          sizeof(spslam_sim3_result), C, C * 4}))
+        return rc;
+    // the uploads read the vectors above: they must be done before those go out of scope
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    spslam_sim3_map M{st.slot<float>(kTcw), st.slot<int32_t>(kSlot), st.slot<int32_t>(kOff), st.slot<int32_t>(kRows),
+                      point_bad ? st.slot<uint8_t>(kBad) : nullptr, st.slot<spslam_local_point>(kPoints)};
+    int rc = spslam_sim3_solver_batch_device(c, 1, st.slot<spslam_sim3_problem>(kProblem), &M,
+                                             st.slot<spslam_keypoint>(kKun), st.slot<int>(kCounts), cap,
+                                             st.slot<int32_t>(kMatch), st.slot<int32_t>(kRand), st.slot<int32_t>(kTable),
+                                             params, st.slot<spslam_sim3_result>(kResult), st.slot<uint8_t>(kInliers),
+                                             nullptr, match12_out ? st.slot<int32_t>(kMatchOut) : nullptr, c->stream);
+    if (rc) return rc;
+    HIP_CHECK(c, hipMemcpyAsync(result, st.slot<void>(kResult), sizeof *result, hipMemcpyDeviceToHost, c->stream));
+    if (kf1->n)
+        HIP_CHECK(c, hipMemcpyAsync(inliers, st.slot<void>(kInliers), (size_t)kf1->n, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    if (match12_out && kf1->n && result->status == SPSLAM_SIM3_FOUND)
+        HIP_CHECK(c, hipMemcpyAsync(match12_out, st.slot<void>(kMatchOut), (size_t)kf1->n * 4, hipMemcpyDeviceToHost,
+                                    c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    *iterations_done = result->iterations_done;
+    *best_inliers = result->best_inliers;
+    return SPSLAM_OK;
+}
+
+int spslam_debug_fill_loop_scratch(spslam_ctx* c, int value) {
+    if (!c) return SPSLAM_ERR_ARG;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    if (c->d_loop_scratch.cap) {
+        HIP_CHECK(c, hipMemsetAsync(c->d_loop_scratch.p, value, c->d_loop_scratch.cap, c->stream));
+        HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    }
     return SPSLAM_OK;
 }
 

@@ -77,4 +77,35 @@ inline const char* loop_check_match12(const int32_t* match12, int n1, int n2) {
     return nullptr;
 }
 
+// one keyframe of Sim3Solver: its pose, keypoints (the octave indexes mvLevelSigma2) and map points; the grid and
+// the descriptors are not read
+inline const char* loop_check_solver_keyframe(const spslam_sim3_keyframe* k, int n_rows, int n_levels) {
+    if (!k) return "a keyframe is missing";
+    if (!k->Tcw) return "Tcw is missing";
+    if (k->n < 0 || k->n > 8192) return "n outside 0 .. 8192";
+    if (k->n && (!k->keys_un || !k->match_row)) return "a keypoint array is missing";
+    for (int i = 0; i < k->n; i++) {
+        if (k->match_row[i] < -1 || k->match_row[i] >= n_rows) return "a map point outside the table";
+        if (k->keys_un[i].octave < 0 || k->keys_un[i].octave >= n_levels) return "an octave outside the configured levels";
+    }
+    return nullptr;
+}
+
+// SetRansacParameters' and iterate's arguments, the solver's state and the recorded draws
+inline const char* loop_check_solver_call(const spslam_sim3_solver_params* p, double probability, int n_iterations,
+                                          const int* iterations_done, const int* best_inliers, const int32_t* rand) {
+    if (!p) return "the parameters are missing";
+    if (p->min_inliers < 3) return "min_inliers below 3";
+    if (p->max_iterations < 1 || p->max_iterations > SPSLAM_SIM3_MAX_ITERATIONS) return "max_iterations outside 1 .. 4096";
+    if (p->rand_max < 1) return "rand_max below 1";
+    if (!(probability > 0.0 && probability < 1.0)) return "probability outside (0, 1)";
+    if (n_iterations < 0) return "n_iterations is negative";
+    if (!iterations_done || !best_inliers) return "the solver's state is missing";
+    if (*iterations_done < 0 || *best_inliers < 0) return "the solver's state is negative";
+    if (!rand) return "the draws are missing";
+    for (int i = 0; i < 3 * p->max_iterations; i++)
+        if (rand[i] < 0 || rand[i] > p->rand_max) return "a draw outside 0 .. rand_max";
+    return nullptr;
+}
+
 }  // namespace spslam

@@ -1,7 +1,8 @@
 """ctypes binding of the loop-closing entries of include/spslam_gpu.h: the four ORBmatcher overloads that
 LoopClosing::ComputeSim3 and SearchAndFuse call -- SearchByBoW(KeyFrame*, KeyFrame*), SearchBySim3,
 SearchByProjection(pKF, Scw, ...) and the search of Fuse(pKF, Scw, ...) -- on keyframe slots, FeatureVectors and the
-map-point table that stay on the device.  Sim3Solver, OptimizeSim3 and the map mutation are the caller's."""
+map-point table that stay on the device -- and Sim3Solver between the first two (RANSAC over Horn's alignment, the
+draws an input).  OptimizeSim3 and the map mutation are the caller's."""
 from __future__ import annotations
 
 import ctypes
@@ -24,6 +25,18 @@ SIM3_MAP_TABLES = (("kf_Tcw", np.float32), ("kf_slot", np.int32), ("match_off", 
 # ComputeSim3: SearchBySim3 at th 7.5 (LoopClosing.cc:325), SearchByProjection at th 10 (:393); SearchAndFuse: th 4 (:700)
 TH_SIM3, TH_PROJECTION, TH_FUSE = 7.5, 10.0, 4.0
 
+# Sim3Solver: struct spslam_sim3_problem / spslam_sim3_result, the statuses, glibc's RAND_MAX
+SIM3_PROBLEM_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("match_offset", "<i4"), ("rand_offset", "<i4"),
+                               ("inlier_offset", "<i4"), ("iterations_done", "<i4"), ("best_inliers", "<i4"),
+                               ("n_iterations", "<i4")])
+SIM3_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n", "<i4"), ("iterations_done", "<i4"), ("best_inliers", "<i4"),
+                              ("n_inliers", "<i4"), ("s12", "<f4"), ("R12", "<f4", 9), ("t12", "<f4", 3),
+                              ("T12", "<f4", 16)])
+assert SIM3_PROBLEM_DTYPE.itemsize == 32 and SIM3_RESULT_DTYPE.itemsize == 136
+SIM3_FOUND, SIM3_NOT_YET, SIM3_NO_MORE = 0, 1, 2
+SIM3_MAX_ITERATIONS = 4096
+RAND_MAX = 2147483647
+
 _P = ctypes.c_void_p
 
 
@@ -33,6 +46,11 @@ class Sim3Map(ctypes.Structure):
 
 class Sim3Params(ctypes.Structure):
     _fields_ = [("th", ctypes.c_float), ("pad", ctypes.c_int32)]
+
+
+class Sim3SolverParams(ctypes.Structure):
+    _fields_ = [("min_inliers", ctypes.c_int32), ("max_iterations", ctypes.c_int32), ("rand_max", ctypes.c_int32),
+                ("fix_scale", ctypes.c_int32)]
 
 
 class BowKeyframe(ctypes.Structure):
@@ -50,7 +68,8 @@ class Sim3Keyframe(ctypes.Structure):
 spslam_gpu.EXPORTED += ["spslam_search_by_bow_kf", "spslam_search_by_bow_kf_batch_device", "spslam_search_by_sim3",
                         "spslam_search_by_sim3_batch_device", "spslam_search_by_projection_sim3",
                         "spslam_search_by_projection_sim3_batch_device", "spslam_fuse_sim3_search",
-                        "spslam_fuse_sim3_search_batch_device"]
+                        "spslam_fuse_sim3_search_batch_device", "spslam_sim3_ransac_table", "spslam_sim3_solver",
+                        "spslam_sim3_solver_batch_device", "spslam_debug_fill_loop_scratch"]
 
 
 def _bind(lib):
@@ -63,6 +82,12 @@ def _bind(lib):
                                                        ctypes.POINTER(Sim3Params), _P, _P, _P]
     lib.spslam_search_by_sim3.argtypes = [_P, ctypes.POINTER(Sim3Keyframe), ctypes.POINTER(Sim3Keyframe), _P, _P, ci,
                                           _P, _P, ctypes.POINTER(Sim3Params), _P, ip]
+    lib.spslam_sim3_ransac_table.argtypes = [ctypes.c_double, ci, ci, ci, _P]
+    lib.spslam_sim3_solver_batch_device.argtypes = [_P, ci, _P, ctypes.POINTER(Sim3Map), _P, _P, ci, _P, _P, _P,
+                                                    ctypes.POINTER(Sim3SolverParams), _P, _P, _P, _P, _P]
+    lib.spslam_sim3_solver.argtypes = [_P, ctypes.POINTER(Sim3Keyframe), ctypes.POINTER(Sim3Keyframe), _P, _P, ci, _P,
+                                       _P, ctypes.POINTER(Sim3SolverParams), ctypes.c_double, ci, ip, ip, _P, _P, _P]
+    lib.spslam_debug_fill_loop_scratch.argtypes = [_P, ci]
     lib.spslam_fuse_sim3_search_batch_device.argtypes = [_P, ci, _P, _P, ci, _P, _P, _P, _P, _P, ci, _P,
                                                          ctypes.POINTER(FuseParams), _P, _P, _P]
     lib.spslam_fuse_sim3_search.argtypes = [_P, _P, _P, ci, _P, _P, ci, _P, _P, _P, ctypes.POINTER(FuseParams), _P, ip]
@@ -146,6 +171,56 @@ class LoopMatcher:
             _ptr(a2), ctypes.byref(p), m.ctypes.data, ctypes.byref(nf)))
         return m[:len(keep[0][0])], nf.value
 
+    # ---- Sim3Solver
+    def sim3_ransac_table(self, cap, probability=0.99, min_inliers=20, max_iterations=300):
+        """mRansacMaxIts for N = 0 .. cap (SetRansacParameters): the table the device form looks N up in."""
+        table = np.zeros(cap + 1, np.int32)
+        self.ex._check(self.ex.lib.spslam_sim3_ransac_table(probability, min_inliers, max_iterations, cap,
+                                                            table.ctypes.data))
+        return table
+
+    def sim3_solver_batch_device(self, n_problems, d_problems, smap: Sim3Map, d_keys_un, d_counts, cap, d_match12,
+                                 d_rand, d_max_its_table, d_results, d_inliers, d_pairs_out=0, d_match12_out=0,
+                                 min_inliers=20, max_iterations=300, fix_scale=True, rand_max=RAND_MAX, stream=0):
+        p = Sim3SolverParams(min_inliers, max_iterations, rand_max, int(fix_scale))
+        self.ex._check(self.ex.lib.spslam_sim3_solver_batch_device(
+            self.ex.ctx, n_problems, d_problems, ctypes.byref(smap), d_keys_un, d_counts, cap, d_match12, d_rand,
+            d_max_its_table, ctypes.byref(p), d_results, d_inliers, d_pairs_out or None, d_match12_out or None,
+            stream or None))
+
+    def sim3_solver(self, kf1, kf2, points, point_bad, match12, rand, n_iterations, state=(0, 0), probability=0.99,
+                    min_inliers=20, max_iterations=300, fix_scale=True, rand_max=RAND_MAX):
+        """One iterate(n_iterations) of a solver whose state (iterations_done, best_inliers) the caller carries.
+        kf: dict(Tcw, kun, match_row).  Returns (result record, inlier bytes, match12 filtered to the inliers or
+        None unless FOUND, the state after)."""
+        keep, rec = [], []
+        for k in (kf1, kf2):
+            kun = np.ascontiguousarray(k["kun"], spslam_gpu.KEYPOINT_DTYPE)
+            T = np.ascontiguousarray(k["Tcw"], np.float32).reshape(16)
+            rows = np.ascontiguousarray(k["match_row"], np.int32)
+            keep.append((kun, T, rows))
+            rec.append(Sim3Keyframe(T.ctypes.data, _ptr(kun), None, None, None, _ptr(rows), len(kun), 0))
+        pts = np.ascontiguousarray(points, LOCAL_POINT_DTYPE)
+        bad = None if point_bad is None else np.ascontiguousarray(point_bad, np.uint8)
+        n1 = len(keep[0][0])
+        m = np.ascontiguousarray(match12, np.int32).reshape(-1)
+        r = np.ascontiguousarray(rand, np.int32).reshape(-1)
+        if len(r) < 3 * max_iterations:
+            raise ValueError("rand holds fewer than 3 * max_iterations values")
+        p = Sim3SolverParams(min_inliers, max_iterations, rand_max, int(fix_scale))
+        done, best = ctypes.c_int(state[0]), ctypes.c_int(state[1])
+        result = np.zeros((), SIM3_RESULT_DTYPE)
+        inliers, out = np.zeros(max(n1, 1), np.uint8), np.zeros(max(n1, 1), np.int32)
+        self.ex._check(self.ex.lib.spslam_sim3_solver(
+            self.ex.ctx, ctypes.byref(rec[0]), ctypes.byref(rec[1]), _ptr(pts), _ptr(bad), len(pts), _ptr(m),
+            r.ctypes.data, ctypes.byref(p), probability, n_iterations, ctypes.byref(done), ctypes.byref(best),
+            result.ctypes.data, inliers.ctypes.data, out.ctypes.data))
+        found = int(result["status"]) == SIM3_FOUND
+        return result, inliers[:n1], out[:n1] if found else None, (done.value, best.value)
+
+    def debug_fill_loop_scratch(self, value):
+        self.ex._check(self.ex.lib.spslam_debug_fill_loop_scratch(self.ex.ctx, value))
+
     # ---- Fuse(pKF, Scw, ...), the search
     def fuse_sim3_search_batch_device(self, n_problems, d_problems, d_points, max_points, d_keys_un, d_desc,
                                       d_grid_off, d_grid_idx, d_counts, cap, d_skip, d_results, d_nfused, th=TH_FUSE,
@@ -194,6 +269,20 @@ class LoopMatcher:
         return match[:len(k)], nm.value
 
 
-__all__ = ["LoopMatcher", "Sim3Map", "Sim3Params", "BowKeyframe", "Sim3Keyframe", "BowSide", "SIM3_PAIR_DTYPE",
+def compute_sim3_round_robin(first_success, per_turn=5):
+    """Which candidate LoopClosing::ComputeSim3's loop (:288-344) reaches first: the candidates take turns of
+    per_turn RANSAC iterations in index order, so a candidate whose solver first succeeds at iteration k (counted
+    from 0; None: never, or discarded) returns its transformation in round k // per_turn.  first_success is, per
+    candidate, result["iterations_done"] - 1 of one device call with n_iterations = max_iterations when its status
+    is SIM3_FOUND, else None.  Returns (candidate, round), or (None, None) when every candidate fails."""
+    turns = [(k // per_turn, i) for i, k in enumerate(first_success) if k is not None]
+    if not turns:
+        return None, None
+    rnd, i = min(turns)
+    return i, rnd
+
+
+__all__ = ["LoopMatcher", "Sim3SolverParams", "SIM3_PROBLEM_DTYPE", "SIM3_RESULT_DTYPE", "SIM3_FOUND", "SIM3_NOT_YET",
+           "SIM3_NO_MORE", "SIM3_MAX_ITERATIONS", "RAND_MAX", "compute_sim3_round_robin", "Sim3Map", "Sim3Params", "BowKeyframe", "Sim3Keyframe", "BowSide", "SIM3_PAIR_DTYPE",
            "SIM3_MAP_TABLES", "FUSE_PROBLEM_DTYPE", "FUSE_RESULT_DTYPE", "LOCAL_POINT_DTYPE", "PROJ_SIM3_KEYS",
            "POINTS_PER_GROUP", "BOW_WAVES", "TH_SIM3", "TH_PROJECTION", "TH_FUSE"]

@@ -149,6 +149,68 @@ int main() {
         expect(loop_check_match12(nullptr, 7, 5), "match12 is missing", "no match12");
         expect(loop_check_match12(nullptr, 0, 5), nullptr, "no match12 and no keypoints");
     }
+    {   // Sim3Solver: the keyframes (octaves against the levels), the call's parameters, the state and the draws
+        for (int n : {0, 1, 7, 64}) {
+            Keyframe k(n);
+            const spslam_sim3_keyframe s = k.sim3();
+            expect(loop_check_solver_keyframe(&s, n, 8), nullptr, "a sound solver keyframe");
+        }
+        Keyframe k(7);
+        spslam_sim3_keyframe s = k.sim3();
+        s.grid_off = nullptr; s.grid_idx = nullptr; s.desc = nullptr;   // not read by the solver
+        expect(loop_check_solver_keyframe(&s, 7, 8), nullptr, "no grid and no descriptors");
+        expect(loop_check_solver_keyframe(nullptr, 7, 8), "keyframe is missing", "no keyframe");
+        expect(loop_check_solver_keyframe(&s, 5, 8), "map point outside", "a row == n_rows");
+        k.rows[1] = -2;
+        expect(loop_check_solver_keyframe(&s, 7, 8), "map point outside", "a row below -1");
+        k.rows[1] = 1;
+        k.keys[6].octave = 8;
+        expect(loop_check_solver_keyframe(&s, 7, 8), "octave outside", "an octave == n_levels");
+        expect(loop_check_solver_keyframe(&s, 7, 9), nullptr, "the octave inside nine levels");
+        k.keys[6].octave = -1;
+        expect(loop_check_solver_keyframe(&s, 7, 8), "octave outside", "a negative octave");
+        k.keys[6].octave = 0;
+        s.n = 8193;
+        expect(loop_check_solver_keyframe(&s, 7, 8), "n outside", "n too large");
+        s = k.sim3();
+        s.Tcw = nullptr;
+        expect(loop_check_solver_keyframe(&s, 7, 8), "Tcw is missing", "no Tcw");
+        s = k.sim3();
+        s.keys_un = nullptr;
+        expect(loop_check_solver_keyframe(&s, 7, 8), "keypoint array", "no keys_un");
+
+        spslam_sim3_solver_params P{20, 300, 2147483647, 1};
+        std::vector<int32_t> draws(3 * 300, 5);
+        draws.back() = 2147483647;
+        int done = 0, best = 0;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), nullptr, "a sound call");
+        expect(loop_check_solver_call(nullptr, 0.99, 5, &done, &best, draws.data()), "parameters are missing", "no parameters");
+        P.min_inliers = 2;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), "min_inliers below 3", "min_inliers 2");
+        P.min_inliers = 3;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), nullptr, "min_inliers 3");
+        P.max_iterations = 0;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), "max_iterations outside", "no iterations");
+        P.max_iterations = SPSLAM_SIM3_MAX_ITERATIONS + 1;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), "max_iterations outside", "too many iterations");
+        P.max_iterations = 300;
+        P.rand_max = 0;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), "rand_max below 1", "rand_max 0");
+        P.rand_max = 2147483647;
+        expect(loop_check_solver_call(&P, 1.0, 5, &done, &best, draws.data()), "probability outside", "probability 1");
+        expect(loop_check_solver_call(&P, 0.99, -1, &done, &best, draws.data()), "n_iterations is negative", "n_iterations -1");
+        expect(loop_check_solver_call(&P, 0.99, 0, &done, &best, draws.data()), nullptr, "n_iterations 0");
+        expect(loop_check_solver_call(&P, 0.99, 5, nullptr, &best, draws.data()), "state is missing", "no state");
+        done = -1;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), "state is negative", "iterations_done -1");
+        done = 0;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, nullptr), "draws are missing", "no draws");
+        draws.back() = -1;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), "draw outside", "a negative last draw");
+        draws.back() = 7;
+        P.rand_max = 6;
+        expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), "draw outside", "a draw above rand_max");
+    }
     if (failures) return 1;
     std::printf("loop_check: all checks hold\n");
     return 0;
