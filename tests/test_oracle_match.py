@@ -24,8 +24,11 @@ from matcher_ref import f32 as _f, fma, mat3, rotation_bin, three_maxima
 K = synth.TUM3
 
 
-def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True):
-    """Transcription of ORBmatcher.cc:1328-1470 + Frame.cc:427-480 in Python."""
+def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True, trace=None):
+    """Transcription of ORBmatcher.cc:1328-1470 + Frame.cc:427-480 in Python.  trace (a dict, optional) receives the
+    intermediate values the case tables assert on: the direction flags, the rotation histogram and its kept bins,
+    and per searched point the projection, the cell range and its candidate keys in the order (distance, scan
+    position) with whether a blocking point held the keypoint when the point was walked."""
     fx, fy, cx, cy, bf, minx, maxx, miny, maxy, gix, giy = [_f(v) for v in geo[:11]]
     scale = [_f(v) for v in geo[11:]]
     n = len(kun)
@@ -39,6 +42,8 @@ def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True)
     bwd = -tlc[2] > mb and not mono
     hist = [[] for _ in range(30)]
     nm = 0
+    if trace is not None:
+        trace.update(fwd=bool(fwd), bwd=bool(bwd), tlc_z=tlc[2], mb=mb, points={})
     for i, p in enumerate(P):
         x3 = mat3(Tcw, p["xw"], c=tcw)
         invz = _f(1.0 / float(x3[2]))
@@ -46,6 +51,8 @@ def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True)
             continue
         u, v = fma(_f(fx * x3[0]), invz, cx), fma(_f(fy * x3[1]), invz, cy)
         if u < minx or u > maxx or v < miny or v > maxy:
+            if trace is not None:
+                trace["points"][i] = dict(u=u, v=v, outside=True, keys=[])
             continue
         o = int(p["octave"])
         r = _f(_f(th) * scale[o])
@@ -67,16 +74,21 @@ def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True)
                     if abs(_f(kun[k]["x"] - u)) < r and abs(_f(kun[k]["y"] - v)) < r:
                         cand.append(k)
         best, bi = 256, -1
-        for k in cand:
-            if match[k] >= 0 and blocking[k]:
+        keys = []
+        for pos, k in enumerate(cand):
+            held = match[k] >= 0 and blocking[k]
+            if held and trace is None:
                 continue
             if ur[k] > 0:
                 urp = fma(-bf, invz, u)
                 if abs(_f(urp - ur[k])) > r:
                     continue
             d = OM.descriptor_distance(p["desc"], desc[k])
-            if d < best:
+            keys.append((d, pos, held))
+            if not held and d < best:
                 best, bi = d, k
+        if trace is not None:
+            trace["points"][i] = dict(u=u, v=v, r=r, cells=(x0, x1, y0, y1), keys=sorted(keys), best=best)
         if best <= 100:
             match[bi] = i
             blocking[bi] = p["n_obs"] > 0
@@ -85,6 +97,8 @@ def py_search(fr, P, kun, desc, ur, go, gi, geo, th, mono=False, check_ori=True)
                 hist[rotation_bin(p["angle"], kun[bi]["angle"])].append(bi)
     if check_ori:
         ind = three_maxima([len(h) for h in hist])
+        if trace is not None:
+            trace.update(hist=[len(h) for h in hist], kept=ind)
         for b in range(30):
             if b not in ind:
                 for k in hist[b]:
@@ -210,13 +224,19 @@ _libm = ctypes.CDLL("libm.so.6")
 _libm.logf.restype, _libm.logf.argtypes = ctypes.c_float, [ctypes.c_float]
 
 
-def py_search_local(fr, P, kun, desc, ur, go, gi, geo, taken, th=3.0, nn=0.8, vcl=0.5):
-    """Transcription of Frame::isInFrustum, MapPoint::PredictScale and ORBmatcher.cc:45-130."""
+def py_search_local(fr, P, kun, desc, ur, go, gi, geo, taken, th=3.0, nn=0.8, vcl=0.5, scale_factor=1.2, n_levels=8,
+                    trace=None):
+    """Transcription of Frame::isInFrustum, MapPoint::PredictScale and ORBmatcher.cc:45-130.  trace (a dict,
+    optional) receives per point why isInFrustum rejected it (None: in view) and, for the points in view, the
+    viewing cosine, PredictScale's level before the clamp, the radius factor, the window, and its candidate keys
+    among the keypoints free on entry in the order (distance, scan position) with whether an earlier point of the
+    list had taken the keypoint."""
     fx, fy, cx, cy, bf, minx, maxx, miny, maxy, gix, giy = [_f(v) for v in geo[:11]]
     scale = [_f(v) for v in geo[11:]]
-    lsf = _f(_libm.logf(_f(1.2)))
+    lsf = _f(_libm.logf(_f(scale_factor)))
     n = len(kun)
     match, tk = [-1] * n, [bool(t) for t in taken]
+    tk0 = list(tk)
     Tcw = fr["Tcw"].reshape(4, 4)
     tcw = Tcw[:3, 3]
     Ow = mat3(Tcw, tcw, transpose=True, sign=-1.0)
@@ -225,24 +245,31 @@ def py_search_local(fr, P, kun, desc, ur, go, gi, geo, taken, th=3.0, nn=0.8, vc
     for i, p in enumerate(P):
         Pc = mat3(Tcw, p["xw"], c=tcw)
         ok = False
-        if Pc[2] >= 0:
-            invz = _f(_f(1.0) / Pc[2])
-            u, v = fma(_f(fx * Pc[0]), invz, cx), fma(_f(fy * Pc[1]), invz, cy)
-            if minx <= u <= maxx and miny <= v <= maxy:
+        why = "behind"
+        if not Pc[2] < 0:
+            with np.errstate(all="ignore"):
+                invz = _f(_f(1.0) / Pc[2])
+                u, v = fma(_f(fx * Pc[0]), invz, cx), fma(_f(fy * Pc[1]), invz, cy)
+            why = "left" if u < minx else "right" if u > maxx else "top" if v < miny else "bottom"
+            if not (u < minx or u > maxx or v < miny or v > maxy):
                 PO = [_f(p["xw"][k] - Ow[k]) for k in range(3)]
                 s = _f(PO[0] * PO[0])
                 s = _f(s + _f(PO[1] * PO[1]))
                 s = _f(s + _f(PO[2] * PO[2]))
                 dist = _f(np.sqrt(np.float64(s)))
+                why = "near" if dist < _f(_f(0.8) * p["min_dist"]) else "far"
                 if not (dist < _f(_f(0.8) * p["min_dist"]) or dist > _f(_f(1.2) * p["max_dist"])):
                     dot = float(PO[0]) * float(p["normal"][0]) + float(PO[1]) * float(p["normal"][1])
                     dot += float(PO[2]) * float(p["normal"][2])
                     vc = _f(dot / float(dist))
+                    why = "view_cos"
                     if not vc < vcl:
                         ok = True
-                        lvl = int(np.ceil(_f(_f(_libm.logf(_f(p["max_dist"] / dist))) / lsf)))
-                        lvl = min(max(lvl, 0), 7)
+                        raw = int(np.ceil(_f(_f(_libm.logf(_f(p["max_dist"] / dist))) / lsf)))
+                        lvl = min(max(raw, 0), n_levels - 1)
         inview.append(ok)
+        if trace is not None:
+            trace[i] = dict(why=None if ok else why)
         if not ok:
             continue
         r = _f(2.5) if vc > _f(0.998) else _f(4.0)
@@ -254,9 +281,13 @@ def py_search_local(fr, P, kun, desc, ur, go, gi, geo, taken, th=3.0, nn=0.8, vc
         x1 = min(63, int(np.ceil(_f(_f(_f(u - minx) + rs) * gix))))
         y0 = max(0, int(np.floor(_f(_f(_f(v - miny) - rs) * giy))))
         y1 = min(47, int(np.ceil(_f(_f(_f(v - miny) + rs) * giy))))
+        if trace is not None:
+            trace[i].update(u=u, v=v, view_cos=vc, raw_level=raw, level=lvl, radius=r, rs=rs, cells=(x0, x1, y0, y1),
+                            keys=[])
         if x0 >= 64 or x1 < 0 or y0 >= 48 or y1 < 0:
             continue
         bd, bl, bd2, bl2, bi = 256, -1, 256, -1, -1
+        pos = -1
         for ix in range(x0, x1 + 1):
             for iy in range(y0, y1 + 1):
                 c = ix * 48 + iy
@@ -267,15 +298,22 @@ def py_search_local(fr, P, kun, desc, ur, go, gi, geo, taken, th=3.0, nn=0.8, vc
                         continue
                     if not (abs(_f(kun[k]["x"] - u)) < rs and abs(_f(kun[k]["y"] - v)) < rs):
                         continue
-                    if tk[k]:
+                    pos += 1
+                    if tk[k] and (trace is None or tk0[k]):
                         continue
                     if ur[k] > 0 and abs(_f(urp - ur[k])) > rs:
                         continue
                     d = OM.descriptor_distance(p["desc"], desc[k])
+                    if trace is not None:
+                        trace[i]["keys"].append((d, pos, tk[k]))
+                        if tk[k]:
+                            continue
                     if d < bd:
                         bd2, bl2, bd, bl, bi = bd, bl, d, o, k
                     elif d < bd2:
                         bd2, bl2 = d, o
+        if trace is not None:
+            trace[i]["keys"].sort()
         if bd <= 100:
             if bl == bl2 and _f(bd) > _f(_f(nn) * _f(bd2)):
                 continue
