@@ -1780,8 +1780,10 @@ int spslam_place_min_score(spslam_ctx* ctx, const spslam_place_db* db, int n_kf,
  *   SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)       src/ORBmatcher.cc:290-403   (LoopClosing.cc:393)
  *   Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)                src/ORBmatcher.cc:977-1100  (LoopClosing.cc:700)
  * All four are deterministic, and so is Sim3Solver (src/Sim3Solver.cc, LoopClosing.cc:276-324) once its rand() draws
- * are an input: it sits between the first two.  OptimizeSim3, the consistency groups and CorrectLoop's map mutation
- * stay with the caller.  None of these entries has a timing kind, and none is part of the batched step.
+ * are an input: it sits between the first two.  Optimizer::OptimizeSim3 (src/Optimizer.cc:2279-2474,
+ * LoopClosing.cc:328) follows SearchBySim3 and leaves the Scw that SearchByProjection takes, so that a candidate goes
+ * from the BoW matches to the Scw search on one stream.  The consistency groups and CorrectLoop's map mutation stay
+ * with the caller.  None of these entries has a timing kind, and none is part of the batched step.
  * KeyFrame's image bounds are ints (include/KeyFrame.h:198-201): the configured bounds are truncated, as for
  * spslam_fuse_search.  The host-pointer forms take one problem and check every index before anything is launched
  * (SPSLAM_ERR_ARG on a violation). */
@@ -1953,6 +1955,66 @@ int spslam_sim3_solver(spslam_ctx* ctx, const spslam_sim3_keyframe* kf1, const s
                        const int32_t* match12, const int32_t* rand, const spslam_sim3_solver_params* params,
                        double probability, int n_iterations, int* iterations_done, int* best_inliers,
                        spslam_sim3_result* result, uint8_t* inliers, int32_t* match12_out);
+
+/* ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:2279-2474) as ComputeSim3 calls it between SearchBySim3 and
+ * SearchByProjection(pKF, Scw, ...), and mg2oScw / mScw of LoopClosing.cc:335-337.  Semantics: tests/sim3_opt_ref.cpp
+ * (DESIGN 3.19): g2o's Levenberg-Marquardt on one VertexSim3Expmap over an EdgeSim3ProjectXYZ and an
+ * EdgeInverseSim3ProjectXYZ per correspondence, numeric Jacobians, Huber kernels of delta sqrt(th2), the dense LDLT;
+ * optimize(5), the chi2 check that removes pairs, optimize(5 or 10), the final check.  All in fp64 with g2o's
+ * summation order; sin / cos are correctly rounded.
+ * fix_scale must be 1 (RGB-D, the only sensor this library runs: mbFixScale = mSensor != MONOCULAR).  Under a fixed
+ * scale the update's sigma is exactly 0 and exp(0) = 1 in every libm; a free scale needs a correctly rounded exp,
+ * which the library does not have, so fix_scale = 0 is refused with SPSLAM_ERR_ARG before anything is launched. */
+#define SPSLAM_SIM3_OPT_OK 0       /* both optimize calls ran; n_in is OptimizeSim3's return value */
+#define SPSLAM_SIM3_OPT_TOO_FEW 1  /* nCorrespondences - nBad < 10 (:2444): returned 0, S12 is the input */
+
+typedef struct spslam_sim3_opt_params {
+    float th2;                 /* 10 in ComputeSim3; > 0 */
+    int32_t fix_scale;         /* must be 1 */
+    int32_t min_inliers;       /* 20 in ComputeSim3: accepted = n_in >= min_inliers */
+    int32_t pad;
+} spslam_sim3_opt_params;
+
+typedef struct spslam_sim3_opt_result {
+    int32_t n_in;              /*   0  the return value (0 when TOO_FEW) */
+    int32_t n_corr;            /*   4  nCorrespondences */
+    int32_t n_bad;             /*   8  nBad of the first check */
+    int32_t status;            /*  12  SPSLAM_SIM3_OPT_* */
+    int32_t accepted;          /*  16  n_in >= min_inliers (LoopClosing.cc:331) */
+    int32_t iterations1;       /*  20  LM iterations of optimize(5) */
+    int32_t trials1;           /*  24  its damping trials in total */
+    int32_t iterations2;       /*  28  the same of the second optimize (0 when TOO_FEW) */
+    int32_t trials2;           /*  32 */
+    int32_t pad;               /*  36 */
+    double S12[8];             /*  40  g2oS12 on return: quaternion x y z w (not normalised), t, s */
+    double Scw[8];             /* 104  mg2oScw = S12 * Sim3(R2w, t2w, 1.0), the same order */
+    float mScw[16];            /* 168  Converter::toCvMat(mg2oScw): [s*R | t; 0 0 0 1] row-major */
+} spslam_sim3_opt_result;      /* 232 bytes */
+
+/* Batched, device resident.  Pair p is the spslam_sim3_pair that spslam_sim3_solver_batch_device leaves and
+ * spslam_search_by_sim3_batch_device reads: kf1, kf2, match_offset, and s12, R12, t12 as gScm's input
+ * (LoopClosing.cc:327); the three calls chain on one stream over the same buffers.  d_match12 is read and rewritten
+ * in place (vpMatches1): keypoint i of KF1 becomes an edge pair, in order, when match12[i] is a keypoint of KF2, both
+ * keypoints have a map point (match_row >= 0) and neither point is bad; an entry that is skipped stays as it was, an
+ * entry whose pair fails either check becomes -1.  CONTRACT, as for SearchBySim3: the points' GetIndexInKeyFrame are
+ * i and match12[i].  The camera and mvInvLevelSigma2 are the context's (one camera: K1 = K2); octaves outside the
+ * configured levels read level 0.  d_results[p] is always written whole: S12 is the optimised estimate, or the
+ * input when the status is TOO_FEW (n_corr = 0 included, where g2o optimises nothing); Scw and mScw are made from
+ * that S12 and KF2's kf_Tcw.  Pairs' match12 ranges must be disjoint.  cap <= 8192.  The call keeps 16 + 104 * cap
+ * bytes of scratch per pair in the context, the buffer the other loop-closing entries use: calls that share a
+ * context are ordered on one stream.  The result does not depend on what the scratch held. */
+int spslam_sim3_optimize_batch_device(spslam_ctx* ctx, int n_pairs, const spslam_sim3_pair* d_pairs,
+                                      const spslam_sim3_map* map, const spslam_keypoint* d_keys_un, const int* d_counts,
+                                      int cap, const spslam_sim3_opt_params* params, int32_t* d_match12,
+                                      spslam_sim3_opt_result* d_results, void* hip_stream);
+
+/* Drop-in for one pair on host buffers: the keyframes' Tcw, keys_un, match_row and n are read (the grid and the
+ * descriptors are not); match12: kf1->n ints in [-1, kf2->n), rewritten in place; pair->s12 / R12 / t12 are read,
+ * its indices and offsets ignored.  Every index, octave and parameter is checked before anything is launched. */
+int spslam_sim3_optimize(spslam_ctx* ctx, const spslam_sim3_keyframe* kf1, const spslam_sim3_keyframe* kf2,
+                         const spslam_local_point* points, const uint8_t* point_bad, int n_rows,
+                         const spslam_sim3_pair* pair, const spslam_sim3_opt_params* params, int32_t* match12,
+                         spslam_sim3_opt_result* result);
 
 /* Test hook: fills the loop-closing scratch of the context with a byte value (results must not depend on it). */
 int spslam_debug_fill_loop_scratch(spslam_ctx* ctx, int value);

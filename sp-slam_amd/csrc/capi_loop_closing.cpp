@@ -2,11 +2,12 @@
 // spslam_search_by_bow_kf[_batch_device] (SearchByBoW(KeyFrame*, KeyFrame*)), spslam_search_by_sim3[_batch_device]
 // (SearchBySim3), spslam_search_by_projection_sim3[_batch_device] (SearchByProjection(pKF, Scw, ...)) and
 // spslam_fuse_sim3_search[_batch_device] (the search of Fuse(pKF, Scw, ...)), and Sim3Solver between the first two:
-// spslam_sim3_ransac_table, spslam_sim3_solver[_batch_device].  The host forms check their indices with loop_check.h
-// before anything is staged.
+// spslam_sim3_ransac_table, spslam_sim3_solver[_batch_device], and Optimizer::OptimizeSim3 with Scw after SearchBySim3:
+// spslam_sim3_optimize[_batch_device].  The host forms check their indices with loop_check.h before anything is staged.
 #include "capi_ctx.h"
 #include "loop_check.h"
 #include "sim3_launch.h"
+#include "sim3_opt_launch.h"
 
 #include <cmath>
 #include <cstring>
@@ -314,6 +315,81 @@ int spslam_sim3_solver(spslam_ctx* c, const spslam_sim3_keyframe* kf1, const sps
     HIP_CHECK(c, hipStreamSynchronize(c->stream));
     *iterations_done = result->iterations_done;
     *best_inliers = result->best_inliers;
+    return SPSLAM_OK;
+}
+
+// ---------------------------------------------------------------- Optimizer::OptimizeSim3 and Scw
+int spslam_sim3_optimize_batch_device(spslam_ctx* c, int n_pairs, const spslam_sim3_pair* d_pairs,
+                                      const spslam_sim3_map* map, const spslam_keypoint* d_keys_un, const int* d_counts,
+                                      int cap, const spslam_sim3_opt_params* params, int32_t* d_match12,
+                                      spslam_sim3_opt_result* d_results, void* hip_stream) {
+    if (!c) return SPSLAM_ERR_ARG;
+    if (!c->frame_ready) return fail(c, SPSLAM_ERR_NOT_READY, "spslam_frame_configure not called%s", "");
+    // fix_scale = 0 needs a correctly rounded exp (include/spslam_gpu.h): refused before anything is launched
+    if (n_pairs < 1 || n_pairs > 65535 || !d_pairs || !map || !map->kf_Tcw || !map->kf_slot || !map->match_off ||
+        !map->match_row || !map->points || !d_keys_un || !d_counts || cap < 1 || cap > 8192 || !params ||
+        params->fix_scale != 1 || !(params->th2 > 0.f) || !d_match12 || !d_results)
+        return fail(c, SPSLAM_ERR_ARG, "bad argument%s", " to spslam_sim3_optimize_batch_device");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    Sim3OptConsts P{};
+    P.fx = c->fg.fx; P.fy = c->fg.fy; P.cx = c->fg.cx; P.cy = c->fg.cy;
+    level_table(c, c->inv_sigma2, P.inv_sigma2);
+    P.th2 = params->th2;
+    P.min_inliers = params->min_inliers;
+    HIP_CHECK(c, c->d_loop_scratch.reserve(sim3_opt_scratch_bytes(n_pairs, cap), s));
+    HIP_CHECK(c, sim3_opt_launch(n_pairs, d_pairs, *map, d_keys_un, d_counts, cap, P, c->d_loop_scratch.p, d_match12,
+                                 d_results, s));
+    return SPSLAM_OK;
+}
+
+int spslam_sim3_optimize(spslam_ctx* c, const spslam_sim3_keyframe* kf1, const spslam_sim3_keyframe* kf2,
+                         const spslam_local_point* points, const uint8_t* point_bad, int n_rows,
+                         const spslam_sim3_pair* pair, const spslam_sim3_opt_params* params, int32_t* match12,
+                         spslam_sim3_opt_result* result) {
+    if (!c || !result || n_rows < 0 || (n_rows && !points)) return SPSLAM_ERR_ARG;
+    const spslam_sim3_keyframe* k[2] = {kf1, kf2};
+    for (int s = 0; s < 2; s++)
+        if (const char* e = loop_check_solver_keyframe(k[s], n_rows, c->p.nlevels)) return fail(c, SPSLAM_ERR_ARG, "spslam_sim3_optimize: %s", e);
+    if (const char* e = loop_check_match12(match12, kf1->n, kf2->n)) return fail(c, SPSLAM_ERR_ARG, "spslam_sim3_optimize: %s", e);
+    if (const char* e = loop_check_opt_call(params, pair)) return fail(c, SPSLAM_ERR_ARG, "spslam_sim3_optimize: %s", e);
+    HIP_CHECK(c, hipSetDevice(c->device));
+    // the two keyframes as slots 0 and 1 of cap keypoints, keyframes 0 and 1 of a two-keyframe map
+    const int cap = std::max(std::max(kf1->n, kf2->n), 1);
+    const size_t C = (size_t)cap, R = (size_t)std::max(n_rows, 1);
+    std::vector<spslam_keypoint> kun(2 * C);
+    std::vector<int32_t> rows(2 * C, -1);
+    float Tcw[32];
+    const int32_t counts[2] = {kf1->n, kf2->n}, slot[2] = {0, 1}, off[3] = {0, cap, 2 * cap};
+    for (int s = 0; s < 2; s++) {
+        if (k[s]->n) {
+            std::memcpy(kun.data() + s * C, k[s]->keys_un, (size_t)k[s]->n * sizeof(spslam_keypoint));
+            std::memcpy(rows.data() + s * C, k[s]->match_row, (size_t)k[s]->n * 4);
+        }
+        std::memcpy(Tcw + 16 * s, k[s]->Tcw, 64);
+    }
+    spslam_sim3_pair Q = *pair;
+    Q.kf1 = 0; Q.kf2 = 1; Q.match_offset = 0; Q.result_offset = 0;
+    enum { kKun, kCounts, kTcw, kSlot, kOff, kRows, kBad, kPoints, kPair, kMatch, kResult };
+    Stage st(c);
+    if (int rc = st.open({{kun.data(), kun.size() * sizeof(spslam_keypoint)}, {counts, 8}, {Tcw, 128}, {slot, 8},
+                          {off, 12}, {rows.data(), rows.size() * 4}, {point_bad, point_bad ? (size_t)n_rows : 0, R},
+                          {points, (size_t)n_rows * sizeof(spslam_local_point), R * sizeof(spslam_local_point)},
+                          {&Q, sizeof Q}, {match12, (size_t)kf1->n * 4, C * 4}, sizeof(spslam_sim3_opt_result)}))
+        return rc;
+    // the uploads read the vectors above: they must be done before those go out of scope
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    spslam_sim3_map M{st.slot<float>(kTcw), st.slot<int32_t>(kSlot), st.slot<int32_t>(kOff), st.slot<int32_t>(kRows),
+                      point_bad ? st.slot<uint8_t>(kBad) : nullptr, st.slot<spslam_local_point>(kPoints)};
+    int rc = spslam_sim3_optimize_batch_device(c, 1, st.slot<spslam_sim3_pair>(kPair), &M, st.slot<spslam_keypoint>(kKun),
+                                               st.slot<int>(kCounts), cap, params, st.slot<int32_t>(kMatch),
+                                               st.slot<spslam_sim3_opt_result>(kResult), c->stream);
+    if (rc) return rc;
+    HIP_CHECK(c, hipMemcpyAsync(result, st.slot<void>(kResult), sizeof *result, hipMemcpyDeviceToHost, c->stream));
+    if (kf1->n)
+        HIP_CHECK(c, hipMemcpyAsync(match12, st.slot<void>(kMatch), (size_t)kf1->n * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = st.close())) return rc;
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
     return SPSLAM_OK;
 }
 

@@ -108,4 +108,13 @@ inline const char* loop_check_solver_call(const spslam_sim3_solver_params* p, do
     return nullptr;
 }
 
+// OptimizeSim3's parameters and the pair record whose s12, R12, t12 are gScm
+inline const char* loop_check_opt_call(const spslam_sim3_opt_params* p, const spslam_sim3_pair* pair) {
+    if (!p) return "the parameters are missing";
+    if (p->fix_scale != 1) return "fix_scale is not 1 (a free scale needs a correctly rounded exp)";
+    if (!(p->th2 > 0.f)) return "th2 is not positive";
+    if (!pair) return "the pair is missing";
+    return nullptr;
+}
+
 }  // namespace spslam

@@ -2,7 +2,8 @@
 LoopClosing::ComputeSim3 and SearchAndFuse call -- SearchByBoW(KeyFrame*, KeyFrame*), SearchBySim3,
 SearchByProjection(pKF, Scw, ...) and the search of Fuse(pKF, Scw, ...) -- on keyframe slots, FeatureVectors and the
 map-point table that stay on the device -- and Sim3Solver between the first two (RANSAC over Horn's alignment, the
-draws an input).  OptimizeSim3 and the map mutation are the caller's."""
+draws an input), and Optimizer::OptimizeSim3 with Scw after SearchBySim3 (g2o's Levenberg-Marquardt on one Sim3 vertex,
+fixed scale).  The consistency groups and the map mutation are the caller's."""
 from __future__ import annotations
 
 import ctypes
@@ -37,6 +38,16 @@ SIM3_FOUND, SIM3_NOT_YET, SIM3_NO_MORE = 0, 1, 2
 SIM3_MAX_ITERATIONS = 4096
 RAND_MAX = 2147483647
 
+# OptimizeSim3: struct spslam_sim3_opt_result, the statuses, ComputeSim3's th2 and acceptance count
+SIM3_OPT_RESULT_DTYPE = np.dtype([("n_in", "<i4"), ("n_corr", "<i4"), ("n_bad", "<i4"), ("status", "<i4"),
+                                  ("accepted", "<i4"), ("iterations1", "<i4"), ("trials1", "<i4"), ("iterations2", "<i4"),
+                                  ("trials2", "<i4"), ("pad", "<i4"), ("S12", "<f8", 8), ("Scw", "<f8", 8),
+                                  ("mScw", "<f4", 16)])
+assert SIM3_OPT_RESULT_DTYPE.itemsize == 232
+SIM3_OPT_OK, SIM3_OPT_TOO_FEW = 0, 1
+SIM3_OPT_TH2, SIM3_OPT_MIN_INLIERS = 10.0, 20
+SIM3_OPT_CORR_BYTES = 104    # scratch per keypoint slot of a pair (plus 16 per pair)
+
 _P = ctypes.c_void_p
 
 
@@ -51,6 +62,11 @@ class Sim3Params(ctypes.Structure):
 class Sim3SolverParams(ctypes.Structure):
     _fields_ = [("min_inliers", ctypes.c_int32), ("max_iterations", ctypes.c_int32), ("rand_max", ctypes.c_int32),
                 ("fix_scale", ctypes.c_int32)]
+
+
+class Sim3OptParams(ctypes.Structure):
+    _fields_ = [("th2", ctypes.c_float), ("fix_scale", ctypes.c_int32), ("min_inliers", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
 
 
 class BowKeyframe(ctypes.Structure):
@@ -69,7 +85,8 @@ spslam_gpu.EXPORTED += ["spslam_search_by_bow_kf", "spslam_search_by_bow_kf_batc
                         "spslam_search_by_sim3_batch_device", "spslam_search_by_projection_sim3",
                         "spslam_search_by_projection_sim3_batch_device", "spslam_fuse_sim3_search",
                         "spslam_fuse_sim3_search_batch_device", "spslam_sim3_ransac_table", "spslam_sim3_solver",
-                        "spslam_sim3_solver_batch_device", "spslam_debug_fill_loop_scratch"]
+                        "spslam_sim3_solver_batch_device", "spslam_debug_fill_loop_scratch", "spslam_sim3_optimize",
+                        "spslam_sim3_optimize_batch_device"]
 
 
 def _bind(lib):
@@ -87,6 +104,10 @@ def _bind(lib):
                                                     ctypes.POINTER(Sim3SolverParams), _P, _P, _P, _P, _P]
     lib.spslam_sim3_solver.argtypes = [_P, ctypes.POINTER(Sim3Keyframe), ctypes.POINTER(Sim3Keyframe), _P, _P, ci, _P,
                                        _P, ctypes.POINTER(Sim3SolverParams), ctypes.c_double, ci, ip, ip, _P, _P, _P]
+    lib.spslam_sim3_optimize_batch_device.argtypes = [_P, ci, _P, ctypes.POINTER(Sim3Map), _P, _P, ci,
+                                                      ctypes.POINTER(Sim3OptParams), _P, _P, _P]
+    lib.spslam_sim3_optimize.argtypes = [_P, ctypes.POINTER(Sim3Keyframe), ctypes.POINTER(Sim3Keyframe), _P, _P, ci, _P,
+                                         ctypes.POINTER(Sim3OptParams), _P, _P]
     lib.spslam_debug_fill_loop_scratch.argtypes = [_P, ci]
     lib.spslam_fuse_sim3_search_batch_device.argtypes = [_P, ci, _P, _P, ci, _P, _P, _P, _P, _P, ci, _P,
                                                          ctypes.POINTER(FuseParams), _P, _P, _P]
@@ -218,6 +239,40 @@ class LoopMatcher:
         found = int(result["status"]) == SIM3_FOUND
         return result, inliers[:n1], out[:n1] if found else None, (done.value, best.value)
 
+    # ---- Optimizer::OptimizeSim3 and Scw
+    def sim3_optimize_batch_device(self, n_pairs, d_pairs, smap: Sim3Map, d_keys_un, d_counts, cap, d_match12, d_results,
+                                   th2=SIM3_OPT_TH2, fix_scale=True, min_inliers=SIM3_OPT_MIN_INLIERS, stream=0):
+        """d_pairs: the records the solver leaves and SearchBySim3 reads; d_match12 is rewritten in place;
+        d_results: n_pairs records of SIM3_OPT_RESULT_DTYPE."""
+        p = Sim3OptParams(th2, int(fix_scale), min_inliers, 0)
+        self.ex._check(self.ex.lib.spslam_sim3_optimize_batch_device(
+            self.ex.ctx, n_pairs, d_pairs, ctypes.byref(smap), d_keys_un, d_counts, cap, ctypes.byref(p), d_match12,
+            d_results, stream or None))
+
+    def sim3_optimize(self, kf1, kf2, points, point_bad, s12, R12, t12, match12, th2=SIM3_OPT_TH2, fix_scale=True,
+                      min_inliers=SIM3_OPT_MIN_INLIERS):
+        """kf: dict(Tcw, kun, match_row).  Returns (result record, match12 after)."""
+        keep, rec = [], []
+        for k in (kf1, kf2):
+            kun = np.ascontiguousarray(k["kun"], spslam_gpu.KEYPOINT_DTYPE)
+            T = np.ascontiguousarray(k["Tcw"], np.float32).reshape(16)
+            rows = np.ascontiguousarray(k["match_row"], np.int32)
+            keep.append((kun, T, rows))
+            rec.append(Sim3Keyframe(T.ctypes.data, _ptr(kun), None, None, None, _ptr(rows), len(kun), 0))
+        pts = np.ascontiguousarray(points, LOCAL_POINT_DTYPE)
+        bad = None if point_bad is None else np.ascontiguousarray(point_bad, np.uint8)
+        pair = np.zeros((), SIM3_PAIR_DTYPE)
+        pair["s12"], pair["R12"], pair["t12"] = s12, np.asarray(R12, np.float32).reshape(9), t12
+        n1 = len(keep[0][0])
+        m = np.array(match12, np.int32).reshape(-1)
+        m = m if len(m) else np.zeros(1, np.int32)
+        p = Sim3OptParams(th2, int(fix_scale), min_inliers, 0)
+        result = np.zeros((), SIM3_OPT_RESULT_DTYPE)
+        self.ex._check(self.ex.lib.spslam_sim3_optimize(
+            self.ex.ctx, ctypes.byref(rec[0]), ctypes.byref(rec[1]), _ptr(pts), _ptr(bad), len(pts), pair.ctypes.data,
+            ctypes.byref(p), m.ctypes.data if n1 else None, result.ctypes.data))
+        return result, m[:n1]
+
     def debug_fill_loop_scratch(self, value):
         self.ex._check(self.ex.lib.spslam_debug_fill_loop_scratch(self.ex.ctx, value))
 
@@ -282,7 +337,8 @@ def compute_sim3_round_robin(first_success, per_turn=5):
     return i, rnd
 
 
-__all__ = ["LoopMatcher", "Sim3SolverParams", "SIM3_PROBLEM_DTYPE", "SIM3_RESULT_DTYPE", "SIM3_FOUND", "SIM3_NOT_YET",
+__all__ = ["LoopMatcher", "Sim3SolverParams", "Sim3OptParams", "SIM3_OPT_RESULT_DTYPE", "SIM3_OPT_OK", "SIM3_OPT_TOO_FEW",
+           "SIM3_OPT_TH2", "SIM3_OPT_MIN_INLIERS", "SIM3_OPT_CORR_BYTES", "SIM3_PROBLEM_DTYPE", "SIM3_RESULT_DTYPE", "SIM3_FOUND", "SIM3_NOT_YET",
            "SIM3_NO_MORE", "SIM3_MAX_ITERATIONS", "RAND_MAX", "compute_sim3_round_robin", "Sim3Map", "Sim3Params", "BowKeyframe", "Sim3Keyframe", "BowSide", "SIM3_PAIR_DTYPE",
            "SIM3_MAP_TABLES", "FUSE_PROBLEM_DTYPE", "FUSE_RESULT_DTYPE", "LOCAL_POINT_DTYPE", "PROJ_SIM3_KEYS",
            "POINTS_PER_GROUP", "BOW_WAVES", "TH_SIM3", "TH_PROJECTION", "TH_FUSE"]

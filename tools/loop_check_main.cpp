@@ -211,6 +211,26 @@ int main() {
         P.rand_max = 6;
         expect(loop_check_solver_call(&P, 0.99, 5, &done, &best, draws.data()), "draw outside", "a draw above rand_max");
     }
+    {   // OptimizeSim3: the parameters and the pair record (the keyframes are the solver's, match12 as above)
+        spslam_sim3_opt_params P{10.f, 1, 20, 0};
+        spslam_sim3_pair pair{};
+        expect(loop_check_opt_call(&P, &pair), nullptr, "a sound OptimizeSim3 call");
+        expect(loop_check_opt_call(nullptr, &pair), "parameters are missing", "no OptimizeSim3 parameters");
+        expect(loop_check_opt_call(&P, nullptr), "pair is missing", "no pair");
+        P.fix_scale = 0;
+        expect(loop_check_opt_call(&P, &pair), "fix_scale is not 1", "fix_scale 0");
+        P.fix_scale = 2;
+        expect(loop_check_opt_call(&P, &pair), "fix_scale is not 1", "fix_scale 2");
+        P.fix_scale = 1;
+        P.th2 = 0.f;
+        expect(loop_check_opt_call(&P, &pair), "th2 is not positive", "th2 0");
+        P.th2 = -10.f;
+        expect(loop_check_opt_call(&P, &pair), "th2 is not positive", "th2 -10");
+        P.th2 = 0.f / 0.f;
+        expect(loop_check_opt_call(&P, &pair), "th2 is not positive", "th2 NaN");
+        P.th2 = 1e-30f;
+        expect(loop_check_opt_call(&P, &pair), nullptr, "a tiny th2");
+    }
     if (failures) return 1;
     std::printf("loop_check: all checks hold\n");
     return 0;
