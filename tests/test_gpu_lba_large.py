@@ -9,7 +9,13 @@ poses (n = 108 / 150: the factorisation's L in global memory past the LDS-reside
 window of 80 keyframes (48 free + 32 fixed: the wide instance with fewer free poses than the narrow one holds), 66, 98
 and 128 free poses (the wide instance past one mask word: n = 396 / 588 / 768, eight and twelve registers per lane),
 and a window with more than 128 free poses (status -2, nothing else written).  And the team split: the same problem
-solved by 1 .. 8 workgroups is bit-identical (every sum keeps its order whatever the split), narrow and wide."""
+solved by 1 .. 8 workgroups is bit-identical (every sum keeps its order whatever the split), narrow and wide.
+
+Every window here is fully dense: synth.lba_problem's room and box planes are seen by every keyframe, so every free
+pose is coupled with every other, Eigen's AMD returns the natural order and the factorisation takes the dense paths
+(factor_dense_packed at n = 108 / 150, factor_solve<K, false> without a permutation above).  Sparse windows -- a
+non-natural order, elimination trees that are not a chain, Schur patterns with missing blocks -- at these sizes are
+tests/test_gpu_lba_geometry.py's."""
 import numpy as np
 import pytest
 
@@ -37,9 +43,10 @@ def _window(n_kf, n_fixed, step=4, n_points=2000, seed=None, planes=True):
                                                          (100, 2, 3, 1200), (130, 2, 3, 900)])
 def test_lba_large_windows_match_oracle(lba, n_kf, n_fixed, step, n_points):
     """Free poses 18 .. 62 on the narrow instance (n = 108 .. 372: one to six registers of the factorisation wave per
-    lane, L past the LDS-resident size), dense covisibility (step 2 / 3: every pose coupled with most others, hundreds
-    of Schur blocks); 80 keyframes of which 32 fixed, and 66 / 98 / 128 free poses on the wide instance (a landmark's
-    blocks and the Schur pattern's rows past one mask word, reduced systems of 396 / 588 / 768 rows)."""
+    lane, L past the LDS-resident size), full covisibility (the planes couple every pose with every other: hundreds of
+    Schur blocks, none missing, the natural order); 80 keyframes of which 32 fixed, and 66 / 98 / 128 free poses on
+    the wide instance (a landmark's blocks and the Schur pattern's rows past one mask word, reduced systems of
+    396 / 588 / 768 rows)."""
     import oracle_lba
     import test_gpu_lba
     P = _window(n_kf, n_fixed, step, n_points=n_points)
