@@ -27,7 +27,7 @@
 
 namespace spslam {
 
-__constant__ int8_t c_pattern[1024] = {
+__constant__ __attribute__((aligned(16))) int8_t c_pattern[1024] = {
 #include "../../include/spslam_brief_pattern.inc"
 };
 __constant__ int c_umax[16];
@@ -452,12 +452,16 @@ constexpr int kCellScoreMax = kCellWinMax - 6;
 // neither the bounds tests nor a per-pixel division remain; out-of-cell neighbours read the zero frame (the
 // reference's n < thr -> 0).  Candidates keep the reference's row-major order: (group, pixel) order.
 constexpr int kScPitchMax = ((kCellScoreMax + 3) & ~3) + 4, kScRowsMax = kCellScoreMax + 2;
+// score loads in flight per lane (even): 1152 pixels per round trip; 63 VGPRs, so the 8 waves per SIMD that
+// the kernel's LDS allows still fit (20 loads: 69 VGPRs, 7 waves)
+constexpr int kCellLoads = 18;
 __global__ __launch_bounds__(256) void fast_cells_kernel(OrbGeom g, uint32_t* __restrict__ cand,
                                                          uint16_t* __restrict__ cand_cnt, int iniTh, int minTh,
                                                          int cid0, int cid1) {  // this launch's cells [cid0, cid1)
     orb_wave_priority();
     __shared__ __attribute__((aligned(16))) uint8_t scs[4][kScRowsMax * kScPitchMax];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // the wave index as a scalar: the cell's geometry and the window's base address stay in SGPRs
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     // XCD-aware order (as level_kernel): a frame's cells, whose windows overlap by 6 pixels, on one L2
     const int nb = gridDim.x, id = xcd_remap(blockIdx.y * nb + blockIdx.x, nb * gridDim.y);
     const int f = id / nb, cid = cid0 + (id - f * nb) * 4 + wave;
@@ -480,26 +484,30 @@ __global__ __launch_bounds__(256) void fast_cells_kernel(OrbGeom g, uint32_t* __
     const int G = (C + 3) >> 2, P = 4 * G + 4;  // groups per row, LDS row pitch (score column c at byte c + 1)
     const uint8_t* smap = L.score + f * L.blur_frame_stride + (size_t)(iniY + 3) * L.bpitch + (iniX + 3);
     uint32_t* sc32 = reinterpret_cast<uint32_t*>(sc);
-    for (int q = lane; q < ((R + 2) * P) >> 2; q += 64) sc32[q] = 0u;
-    wave_sync();
     const float invC = 1.f / (float)max(C, 1);   // p / C exactly for p < 2^12
-    for (int p0 = 0; p0 < npx; p0 += 256) {
-        uint8_t v[4];
-        int at[4];
+    // kCellLoads byte loads per lane are issued before the first of them is stored to LDS: one memory round
+    // trip per 64 * kCellLoads pixels (a 640x480 pyramid's windows: 961 .. 1089 scored pixels on levels 0-6, one
+    // group; 1258 on level 7, two).
+    // Loads and LDS stores are unconditional: a lane past the window's end reads the last pixel again and
+    // stores it where it belongs once more.  The LDS offsets (< 2^16) wait two to a register.  The zero frame
+    // is written while the first group is on its way.  (No window pixel: nothing reads the LDS.)
+    for (int p0 = 0; p0 < npx; p0 += 64 * kCellLoads) {
+        uint8_t v[kCellLoads];
+        uint32_t at[kCellLoads / 2];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int p = p0 + lane + 64 * k;
-            v[k] = 0;
-            at[k] = -1;
-            if (p < npx) {
-                const int r = (int)(((float)p + 0.5f) * invC), c = p - r * C;
-                v[k] = smap[(size_t)r * L.bpitch + c];
-                at[k] = (r + 1) * P + c + 1;
-            }
+        for (int k = 0; k < kCellLoads; k++) {
+            const int pc = min(p0 + lane + 64 * k, npx - 1);
+            const int r = (int)(((float)pc + 0.5f) * invC), c = pc - __mul24(r, C);   // every factor < 2^13
+            v[k] = smap[(uint32_t)(__mul24(r, L.bpitch) + c)];
+            const uint32_t a = (uint32_t)(__mul24(r + 1, P) + c + 1);
+            at[k >> 1] = (k & 1) ? at[k >> 1] | (a << 16) : a;
+        }
+        if (p0 == 0) {
+            for (int q = lane; q < ((R + 2) * P) >> 2; q += 64) sc32[q] = 0u;
+            wave_sync();
         }
 #pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (at[k] >= 0) sc[at[k]] = v[k];
+        for (int k = 0; k < kCellLoads; k++) sc[(k & 1) ? at[k >> 1] >> 16 : at[k >> 1] & 0xffffu] = v[k];
     }
     wave_sync();
     const int ngroups = R * G;
@@ -1029,6 +1037,15 @@ __device__ float fast_atan2(float y, float x) {
 
 // One wave per keypoint slot: orientation on the level image, rotated BRIEF
 // on the blurred level, final scaling/placement in reference order.
+//
+// The kernel is a chain of memory round trips and little else, so every round trip carries all the loads
+// that do not depend on one another ("Dependent-load chains under load"):
+//   1. the frame's level counts (one lane per level), the slot's keypoint and the lane's four BRIEF tests;
+//   2. the whole 31 x 31 patch of IC_Angle, 16 byte loads per lane, no branch between them;
+//   3. the eight BRIEF samples of the lane, then the four ballots and one descriptor store.
+// Every retained keypoint lies in [19, w - 20] x [19, h - 20] of its level (fast_cells_kernel: window column
+// c < C = maxX - iniX - 6 with iniX >= 16 and maxX <= w - 16), so the square x - 15 .. x + 16, y - 15 .. y + 15
+// the lanes load lies inside the level image of the same frame; the circle is applied to the loaded values.
 __global__ __launch_bounds__(256) void desc_kernel(OrbGeom g, const LevelKp* __restrict__ lvl_kp,
                                                    const int* __restrict__ lvl_cnt, spslam_keypoint* __restrict__ out_kp,
                                                    uint8_t* __restrict__ out_desc, int* __restrict__ out_cnt,
@@ -1039,65 +1056,89 @@ __global__ __launch_bounds__(256) void desc_kernel(OrbGeom g, const LevelKp* __r
     const int gx = (g.lvl_kp_per_frame + 3) / 4;
     const int lid = xcd_remap(blockIdx.x, gridDim.x);
     const int f = lid / gx, lane = threadIdx.x & 63;
-    const int slot = (lid - f * gx) * 4 + (threadIdx.x >> 6);
+    const int slot = (lid - f * gx) * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (slot >= g.lvl_kp_per_frame) return;
+    // the slot's level: kp_base grows with the level, so the level is the number of bases at or below the slot
+    // (every base read from the kernel argument in one batch, no branch between the reads)
     int l = 0;
-    for (int k = 1; k < g.nlevels; k++)
-        if (slot >= g.lv[k].kp_base) l = k;
+#pragma unroll
+    for (int k = 1; k < kMaxLevels; k++) l += (k < g.nlevels && slot >= g.lv[k].kp_base) ? 1 : 0;
     const LevelGeom& L = g.lv[l];
     const int i = slot - L.kp_base;
-    const int* cnt = lvl_cnt + f * kMaxLevels;
-    int off = 0, total = 0;
-    for (int k = 0; k < g.nlevels; k++) {
-        if (k < l) off += cnt[k];
-        total += cnt[k];
+    // lane k < nlevels holds level k's count; the keypoint and the lane's tests k * 64 + lane (one dword each:
+    // x0, y0, x1, y1) are fetched in the same round trip -- an empty slot's keypoint is read and dropped
+    const int cl = lvl_cnt[f * kMaxLevels + (lane & (kMaxLevels - 1))];
+    const LevelKp kp = lvl_kp[(size_t)f * g.lvl_kp_per_frame + slot];
+    uint32_t pat[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) pat[k] = reinterpret_cast<const uint32_t*>(c_pattern)[lane + 64 * k];
+    int off = 0, total = 0, nl = 0;
+#pragma unroll
+    for (int k = 0; k < kMaxLevels; k++) {
+        const int ck = k < g.nlevels ? __builtin_amdgcn_readlane(cl, k) : 0;
+        off += k < l ? ck : 0;
+        nl = k == l ? ck : nl;
+        total += ck;
     }
     if (slot == 0 && lane == 0) out_cnt[f] = min(total, cap_per_frame);
-    if (i >= cnt[l] || off + i >= cap_per_frame) return;
-    const LevelKp kp = lvl_kp[(size_t)f * g.lvl_kp_per_frame + slot];
-    // IC_Angle (:77-104) on the un-blurred level
+    if (i >= nl || off + i >= cap_per_frame) return;
+    // IC_Angle (:77-104) on the un-blurred level: lanes 0-30 take the columns u = -15 .. 15 of the centre row
+    // and the rows below it, lanes 32-62 those of the rows above; lanes 31 and 63 (u = 16) load like the
+    // others and count nothing.  m01 and m10 are integer sums, so the order of the terms is free.
     const uint8_t* img = L.img + f * L.frame_stride;
     const int P = L.stride;
-    const uint8_t* center = img + (size_t)kp.y * P + kp.x;
-    int m10 = 0, m01 = 0;
-    if (lane < 31) {
-        const int u = lane - 15;
-        m10 = u * center[u];
-        for (int v = 1; v <= 15; v++) {
-            if (abs(u) > c_umax[v]) continue;
-            const int vp = center[u + v * P], vm = center[u - v * P];
-            m01 += v * (vp - vm);
-            m10 += u * (vp + vm);
-        }
+    const bool up = lane >= 32;
+    const int u = (lane & 31) - 15, au = abs(u);
+    const uint8_t* col = img + (size_t)kp.y * P + kp.x + u;
+    const int step = up ? -P : P;
+    int px[16];
+#pragma unroll
+    for (int v = 0; v < 16; v++) px[v] = col[v * step];
+    int umax[16];
+#pragma unroll
+    for (int v = 0; v < 16; v++) umax[v] = c_umax[v];
+    int su = up || au > 15 ? 0 : px[0], sv = 0;   // sum of the lane's pixels inside the circle, and of v * pixel
+#pragma unroll
+    for (int v = 1; v < 16; v++) {
+        const int t = au <= umax[v] ? px[v] : 0;
+        su += t;
+        sv += v * t;
     }
+    int m10 = u * su, m01 = up ? -sv : sv;
 #pragma unroll
     for (int off2 = 32; off2 >= 1; off2 >>= 1) {
         m10 += __shfl_xor(m10, off2);
         m01 += __shfl_xor(m01, off2);
     }
+    // wave-uniform from here on: the table reads of glibc_sincosf become scalar loads
+    m10 = __builtin_amdgcn_readfirstlane(m10);
+    m01 = __builtin_amdgcn_readfirstlane(m01);
     const float angle = fast_atan2((float)m01, (float)m10);
-    // rotated BRIEF (:107-147) on the blurred level
+    // rotated BRIEF (:107-147) on the blurred level: the lane's eight samples loaded, then the four compares
     const float factorPI = (float)(M_PI / 180.f);
     float sb, ca;
     glibc_sincosf(angle * factorPI, &sb, &ca);
     const uint8_t* bimg = L.blur + f * L.blur_frame_stride;
     const uint8_t* bc = bimg + (size_t)kp.y * L.bpitch + kp.x;
     const size_t o = (size_t)f * cap_per_frame + off + i;
-    uint64_t* dd = reinterpret_cast<uint64_t*>(out_desc + o * 32);
+    int val[4][2];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int tst = lane + 64 * k;
-        int val[2];
 #pragma unroll
         for (int e = 0; e < 2; e++) {
-            const float x = (float)c_pattern[4 * tst + 2 * e], y = (float)c_pattern[4 * tst + 2 * e + 1];
+            const float x = (float)(int8_t)(pat[k] >> (16 * e)), y = (float)(int8_t)(pat[k] >> (16 * e + 8));
             const int r = cv_round(__builtin_fmaf(x, sb, y * ca));
             const int c = cv_round(__builtin_fmaf(x, ca, -(y * sb)));
-            val[e] = bc[r * L.bpitch + c];
+            val[k][e] = bc[r * L.bpitch + c];
         }
-        const unsigned long long m = __ballot(val[0] < val[1]);
-        if (lane == 0) dd[k] = m;
     }
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const unsigned long long m = __ballot(val[k][0] < val[k][1]);
+        if (lane == k) mine = m;
+    }
+    if (lane < 4) reinterpret_cast<uint64_t*>(out_desc + o * 32)[lane] = mine;
     if (lane == 0) {
         spslam_keypoint r;
         float x = (float)kp.x, y = (float)kp.y;
