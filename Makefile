@@ -12,8 +12,8 @@ CSRC := $(PKG)/csrc
 OBJDIR := build/obj
 KERNELS := orb_kernels pose_kernels plane_kernels plane_segment supposed_kernels frame_kernels lba_kernels lba_g2o lba_g2o_wide \
            assoc_kernels match_kernels map_point_kernels track_kernels local_map_kernels grab_kernels bow_kernels triangulate_kernels covis_kernels \
-           place_kernels sim3_kernels sim3_opt_kernels
-HOST_SRCS := capi_core capi_orb_frame capi_planes capi_solve capi_match capi_track capi_bow capi_local_mapping capi_place capi_loop_closing spslam_step
+           place_kernels sim3_kernels sim3_opt_kernels pnp_kernels
+HOST_SRCS := capi_core capi_orb_frame capi_planes capi_solve capi_match capi_track capi_bow capi_local_mapping capi_place capi_loop_closing capi_reloc spslam_step
 GPU_HDRS := $(wildcard $(CSRC)/*.h) include/spslam_gpu.h include/spslam_brief_pattern.inc
 
 all: $(PKG)/libspslam_gpu.so oracle/liboracle.so tests/shim/libreference_shim.so

@@ -2019,6 +2019,100 @@ int spslam_sim3_optimize(spslam_ctx* ctx, const spslam_sim3_keyframe* kf1, const
 /* Test hook: fills the loop-closing scratch of the context with a byte value (results must not depend on it). */
 int spslam_debug_fill_loop_scratch(spslam_ctx* ctx, int value);
 
+/* ---- PnPsolver (src/PnPsolver.cc), the third call of Tracking::Relocalization (src/Tracking.cc:1573-1734), between
+ * SearchByBoW(KeyFrame, Frame) and PoseOptimization: the constructor, SetRansacParameters and iterate with Refine.
+ * Semantics: tests/pnp_ref.cpp: EPnP in fp64 over the readings of OpenCV's SVD written down there.
+ * The draws are an input, as for Sim3Solver: 4 raw rand() values per iteration, iteration k (counted from 0 over
+ * the solver's life) uses values 4k .. 4k+3.  All hypotheses of a call are evaluated, then Refine once per mask the
+ * sequential loop would try, and the iteration at which that loop returns is selected.
+ * What crosses calls is the caller's: iterations_done, best_inliers, best_Tcw and the best mask (mvbBestInliers:
+ * one byte per kept correspondence, in the constructor's order, which is the same at every call on the same
+ * inputs). */
+#define SPSLAM_PNP_REFINED 0        /* Refine succeeded: Tcw is mRefinedTcw, bNoMore false */
+#define SPSLAM_PNP_BEST_NO_MORE 1   /* bNoMore, mBestTcw returned with the best mask */
+#define SPSLAM_PNP_NO_MORE 2        /* bNoMore, empty Mat: N < mRansacMinInliers, or no hypothesis qualified */
+#define SPSLAM_PNP_OUT_OF_DRAWS 3   /* the call's range passes rand_iterations: the state as far as it got */
+#define SPSLAM_PNP_MAX_ITERATIONS 4096
+
+typedef struct spslam_pnp_problem {
+    int32_t kf;                /* keyframe index of the map (its GetMapPointMatches are the match's points) */
+    int32_t frame_slot;        /* the frame's slot in d_frame_keys_un / d_frame_counts */
+    int32_t match_offset;      /* vpMapPointMatches: frame.cap ints at d_match + match_offset, a keyframe keypoint or -1 */
+    int32_t rand_offset;       /* 4 * rand_iterations ints at d_rand + rand_offset */
+    int32_t inlier_offset;     /* vbInliers: bytes at d_inliers + inlier_offset, ints at d_frame_points + inlier_offset */
+    int32_t best_mask_offset;  /* mvbBestInliers: cap bytes at d_best_mask + best_mask_offset */
+    int32_t iterations_done;   /* mnIterations on entry (0 for a new solver) */
+    int32_t best_inliers;      /* mnBestInliers on entry (0 for a new solver) */
+    int32_t n_iterations;      /* iterate's nIterations, at most params->max_iterations */
+    int32_t rand_iterations;   /* the iterations that the draws cover */
+    int32_t pad[2];
+    float best_Tcw[16];        /* mBestTcw on entry (zeros for a new solver) */
+} spslam_pnp_problem;          /* 112 bytes */
+
+typedef struct spslam_pnp_result {
+    int32_t status;            /* SPSLAM_PNP_* */
+    int32_t n;                 /* N: the correspondences the constructor kept */
+    int32_t iterations_done;   /* mnIterations on exit */
+    int32_t best_inliers;      /* mnBestInliers on exit */
+    int32_t n_inliers;         /* nInliers (0 unless a pose is returned) */
+    int32_t iteration;         /* the iteration that returned a refined pose, else -1 */
+    int32_t min_inliers;       /* mRansacMinInliers for this N */
+    int32_t max_its;           /* mRansacMaxIts for this N (0 when N < min_inliers) */
+    float best_Tcw[16];        /* mBestTcw on exit, row-major */
+    float Tcw[16];             /* the returned Mat as convertTo(CV_32F) rounds it; zeros when empty */
+} spslam_pnp_result;           /* 160 bytes */
+
+typedef struct spslam_pnp_params {
+    int32_t min_inliers;       /* SetRansacParameters' minInliers (10 in Relocalization) */
+    int32_t max_iterations;    /* maxIterations (300), 1 .. SPSLAM_PNP_MAX_ITERATIONS */
+    int32_t min_set;           /* minSet: must be 4 */
+    int32_t rand_max;          /* the caller's RAND_MAX */
+    float epsilon;             /* 0.5 */
+    float th2;                 /* 5.991 */
+} spslam_pnp_params;
+
+/* SetRansacParameters (:121-157) for every N a frame can give, N = 0 .. cap, with the reference's expressions on
+ * the host's libm: min_inliers_n[N] = max(int(N * epsilon), min_inliers, min_set) (an int times a float);
+ * max_its[N] = max(1, min(ceil(log(1-p) / log(1 - pow(eps, 3))), max_iterations)) with eps = max(epsilon,
+ * (float)min_inliers_n / N) in float, 1 when min_inliers_n == N, and 0 where N < min_inliers_n (iterate returns at
+ * once).  A quotient that no int holds counts as max_iterations.  Both tables: cap + 1 ints. */
+int spslam_pnp_ransac_table(double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                            int cap, int32_t* max_its, int32_t* min_inliers_n);
+
+/* Batched, device resident.  Problem p reads d_match as spslam_search_by_bow_batch_device leaves it.  The
+ * constructor keeps frame keypoint i, in order, when match[i] is a keypoint of the keyframe whose match_row is a
+ * point row that is not bad; mvP2D is d_frame_keys_un's x, y, mvSigma2 the context's mvLevelSigma2 at its octave
+ * (octaves outside the configured levels read level 0), the camera the context's.  d_frame_counts[slot] keypoints
+ * of cap per slot.  d_max_its_table / d_min_inliers_table: cap + 1 ints each of spslam_pnp_ransac_table.
+ * Outputs: d_results[p]; d_inliers (always written: the frame's count of bytes, zero unless a pose is returned);
+ * d_best_mask, read when best_inliers qualifies and rewritten when a hypothesis of the call sets a new best;
+ * d_frame_points (may be NULL): for a problem that returns a pose, the frame's mvpMapPoints of Tracking.cc:1661-1670
+ * as ints -- the match's point row where vbInliers, -1 elsewhere -- and untouched otherwise.
+ * Only min_set == 4 is built; a draw outside [0, rand_max] is clamped into the list it indexes.  cap <= 8192.
+ * The call keeps 16 + 32 * cap + 104 * max_iterations bytes of scratch per problem in the context, the buffer the
+ * loop-closing entries use: calls that share a context are ordered on one stream.  The result does not depend on
+ * what the scratch held. */
+int spslam_pnp_solver_batch_device(spslam_ctx* ctx, int n_problems, const spslam_pnp_problem* d_problems,
+                                   const spslam_sim3_map* map, const spslam_keypoint* d_frame_keys_un,
+                                   const int* d_frame_counts, int cap, const int32_t* d_match, const int32_t* d_rand,
+                                   const int32_t* d_max_its_table, const int32_t* d_min_inliers_table,
+                                   const spslam_pnp_params* params, spslam_pnp_result* d_results, uint8_t* d_inliers,
+                                   uint8_t* d_best_mask, int32_t* d_frame_points, void* hip_stream);
+
+/* Drop-in for one problem on host buffers.  keys_un: the frame's n_frame keypoints; match: n_frame ints in
+ * [-1, n_kf); kf_match_row: the keyframe's n_kf map points as rows in [-1, n_rows); rand: 4 * problem->rand_iterations
+ * values in [0, rand_max]; problem's state fields are read (its indices and offsets ignored); best_mask: n_frame
+ * bytes, in and out; inliers: n_frame bytes; frame_points (may be NULL): n_frame ints, written when a pose is
+ * returned.  Every index, octave, parameter and the draw count (rand_iterations >= 1, every value in range) is checked
+ * before anything is launched.  Draws that end inside the call's range are no error of the arguments: whether the
+ * loop needs them depends on where it returns, so the call is launched and reports SPSLAM_PNP_OUT_OF_DRAWS, or
+ * REFINED when a success comes first, as the batched form does. */
+int spslam_pnp_solver(spslam_ctx* ctx, const spslam_keypoint* keys_un, int n_frame, const int32_t* match,
+                      const int32_t* kf_match_row, int n_kf, const spslam_local_point* points,
+                      const uint8_t* point_bad, int n_rows, const int32_t* rand, const spslam_pnp_params* params,
+                      double probability, const spslam_pnp_problem* problem, spslam_pnp_result* result,
+                      uint8_t* inliers, uint8_t* best_mask, int32_t* frame_points);
+
 /* ---- SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) and the search of Fuse(pKF, Scw, vpPoints, th,
  * vpReplacePoint).  Both take spslam_fuse_problem records whose Tcw field holds Scw; the decomposition (:298-303,
  * :985-990: scw, Rcw = sRcw/scw, tcw = col3/scw, Ow) is made on the device.  The keyframe's uright is not read. */
